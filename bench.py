@@ -5,11 +5,15 @@ RCCL gradient all-reduce (N>1, overlapped with backward), clip_grad_norm_(0.1), 
 BASELINE config 2 (ResNet-50 + 6/6 encoder/decoder, d_model 256, 640x640 RefCOCO-shaped
 synthetic batch of 16 per GPU, bf16 operands / fp32 master weights, dropout 0.1), or with
 ``--workload cfg4`` the per-GPU slice of config 4 (ResNet-101 + 6/6, d_model 512, 800x800,
-batch 8).  Also reported: greedy-decode refs/sec on config 5 (ResNet-50 dilation=True 224x224,
-batch 64, 127 steps) in bf16 and in fp32 parity mode, beam 5, and the CPU oracle timed on this
-host's cores (training step and the reference decode algorithm).
+batch 8).  A plain run sets up, warms up, times the K steps and prints the result line; with
+``--dump-outputs DIR`` it also writes what the last timed step left its caller (the loss and the
+norms of the updated parameters) as DIR/<name>.npy.  ``--full`` adds everything else that is reported: the
+per-kernel probe and roofline (an eager re-run of the step), greedy-decode refs/sec on config 5
+(ResNet-50 dilation=True 224x224, batch 64, 127 steps) in bf16 and in fp32 parity mode, beam 5,
+and the CPU oracle timed on this host's cores (training step and the reference decode algorithm).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg4] [--full]
+                    [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...    (one process per GPU, RCCL)
 Rank 0 prints one JSON line.
 """
@@ -94,6 +98,26 @@ def make_optimizer(model, cfg, capturable=False, fused=False):
                              capturable=capturable)
 
 
+def dump_outputs(path, loss, model):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy --
+    ``loss`` (float32 [1], the step's return value) and ``param_norms`` (float64, the L2 norm of
+    every trainable parameter as the step's update left it, named_parameters order).
+
+    Both repeat from run to run of one build to about 1e-5 relative (measured: 1e-6 .. 2e-5
+    after 25 steps of cfg2), which is what the default mode's atomic split-K weight-gradient
+    sums allow: after one step parameters differ in the last bit only, but AdamW's normalised
+    update turns a last-bit difference in a near-zero gradient into a whole +-lr step, so after
+    tens of steps single parameter VALUES differ between two runs by up to ~lr (75x relative on
+    small elements) and are no output two builds could be compared by; their norms are."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = [p.detach() for p in model.parameters() if p.requires_grad]
+    norms = torch.stack([p.double().norm() for p in params])
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "param_norms.npy"), norms.cpu().numpy())
+    return ["loss", "param_norms"]
+
+
 def train_bench(args, rank, world, device):
     from retr_amd.engine import GraphedTrainStep, train_step
     cfg = WORKLOADS[args.workload][0]()
@@ -129,6 +153,7 @@ def train_bench(args, rank, world, device):
             return graph_step(samples, caps, cap_mask)
         return eager_step()
 
+    loss = None
     for _ in range(args.warmup):
         loss = step()
     if (graph_step is not None and graph_step.input_buffers() is not None
@@ -139,7 +164,7 @@ def train_bench(args, rank, world, device):
         samples = (NestedTensor(st[0], st[1]),)
         caps, cap_mask = st[2], st[3]
     torch.cuda.synchronize()
-    assert torch.isfinite(loss).item(), "non-finite loss in warmup"
+    assert loss is None or torch.isfinite(loss).item(), "non-finite loss in warmup"
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -155,15 +180,22 @@ def train_bench(args, rank, world, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     loss_v = float(loss.item())
-    # per-kernel HIP-event timing needs host-side launches: after the timed region, re-run the
-    # identical step eagerly (same weights / inputs / stream) with the probe on
-    pr = probe_mod.Probe(detail=bool(args.probe_detail))
-    with pr:
-        for _ in range(args.probe_steps):
-            eager_step()
-    torch.cuda.synchronize()
-    fam = pr.summary()
-    if args.probe_detail and rank == 0:
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below steps the model again: the state the last timed step left
+        dumped = dump_outputs(args.dump_outputs, loss, model)
+    if args.probe_steps <= 0:
+        fam = {}
+    else:
+        # per-kernel HIP-event timing needs host-side launches: after the timed region, re-run
+        # the identical step eagerly (same weights / inputs / stream) with the probe on
+        pr = probe_mod.Probe(detail=bool(args.probe_detail))
+        with pr:
+            for _ in range(args.probe_steps):
+                eager_step()
+        torch.cuda.synchronize()
+        fam = pr.summary()
+    if fam and args.probe_detail and rank == 0:
         nst = max(1, args.probe_steps)
         with open(args.probe_detail, "w") as f:
             for k, v in sorted(fam.items(), key=lambda kv: -kv[1]["ms_total"]):
@@ -185,7 +217,7 @@ def train_bench(args, rank, world, device):
         sched = {"segments": len(graph_step.segments),
                  "buckets": len(graph_step.schedule["bucket_numel"]),
                  "checked_across_ranks": world}
-    return dt, loss_v, fam, max(1, args.probe_steps), sched
+    return dt, loss_v, fam, max(1, args.probe_steps), sched, dumped
 
 
 def decode_step_bytes(cfg, B, S, T, esize):
@@ -457,11 +489,19 @@ def init_dist(local, backend="nccl"):
         dist.init_process_group(backend, timeout=DIST_TIMEOUT)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line.  Without ``--full`` the run is the plain one: the probe, the decode
+    block and the CPU baselines are off, and asking for one of them is an error."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-kernel probe "
+                         "and roofline, the cfg5 decode block and the CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's loss and the L2 norm of every parameter "
+                         "it updated as DIR/<name>.npy")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg2",
                     help="cfg2 (default, BASELINE metric) or cfg4's per-GPU slice")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (0: the workload's)")
@@ -476,7 +516,8 @@ def main():
                     help="CPU-baseline sample: timed oracle steps (>= 2) until this much time")
     ap.add_argument("--cpu-batch", type=int, default=0, help="CPU-baseline batch (0: --batch)")
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture of the step")
-    ap.add_argument("--probe-steps", type=int, default=2)
+    ap.add_argument("--probe-steps", type=int, default=None,
+                    help="eager steps re-run under the per-kernel probe (--full; default 2)")
     ap.add_argument("--torch-adamw", action="store_true",
                     help="torch.optim.AdamW(capturable) + clip_grad_norm_ instead of the default "
                          "retr_amd FusedAdamW (clip + AdamW kernels over flat arenas)")
@@ -484,13 +525,26 @@ def main():
     ap.add_argument("--stage-inputs", action="store_true",
                     help="copy the batch into the captured step's input buffers every step "
                          "(the pre-round-4 timing; default: the batch already sits there)")
-    args = ap.parse_args()
-    _, size, batch, wl_desc = WORKLOADS[args.workload]
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        if args.probe_detail or (args.probe_steps or 0) > 0:
+            ap.error("--probe-detail / --probe-steps need --full (the probe runs only there)")
+        args.probe_steps, args.no_decode, args.no_cpu_baseline = 0, True, True
+    elif args.probe_steps is None:
+        args.probe_steps = 2
+    _, size, batch, _ = WORKLOADS[args.workload]
     args.size = args.size or size
     args.batch = args.batch or batch
     if args.workload != "cfg2":
         args.no_decode = True                  # the decode block is config 5's
+    return args
 
+
+def main():
+    args = parse_args()
+    wl_desc = WORKLOADS[args.workload][3]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -499,7 +553,7 @@ def main():
     device = torch.device("cuda", local)
     torch.manual_seed(42 + rank)
 
-    dt, loss, fam, psteps, sched = train_bench(args, rank, world, device)
+    dt, loss, fam, psteps, sched, dumped = train_bench(args, rank, world, device)
     imgs = world * args.batch * args.steps
     value = imgs / dt
     roof = _roofline(fam, psteps, args.workload)
@@ -573,7 +627,8 @@ def main():
         out = {"metric": METRIC, "value": round(value, 2), "unit": "images/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-               "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
+               "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "full": args.full,
+               "outputs_dumped": dumped,
                "data": "synthetic (RefCOCO-shaped images/captions, synthetic weights)",
                "config": {"workload": f"{wl_desc}, batch {args.batch}/GPU, "
                                       "fwd+CE+bwd+allreduce+clip+AdamW",

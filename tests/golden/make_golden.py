@@ -26,7 +26,7 @@ from oracle.tv_resnet import install_torchvision_standin  # noqa: E402
 from retr_amd.synthetic import (synthetic_captions, synthetic_images,  # noqa: E402
                                 synthetic_state_dict)
 from tests.helpers import (F2_CASE, PARITY_CASES, VARIANT_CASES, f2_inputs,  # noqa: E402
-                           make_config, variant_config, variant_inputs)
+                           make_config, save_golden, variant_config, variant_inputs)
 
 SMALL_GRADS = ("input_proj.bias", "transformer.decoder.norm.weight", "mlp.layers.2.bias",
                "transformer.embeddings.position_embeddings.weight",
@@ -98,9 +98,8 @@ def make_case(name, caption, utils, decode):
                                     eos_token=eos)
                 out[f"greedy/eos{i}"] = ids.numpy()
         out["greedy_eos"] = np.array(eos_list)
-    path = os.path.join(HERE, f"{name}.npz")
-    np.savez_compressed(path, **out)
-    print(f"wrote {path} ({os.path.getsize(path) / 1e3:.0f} kB) loss={out['loss']:.6f}")
+    for path in save_golden(name, out):    # kept under 1 MiB per file (tests.helpers)
+        print(f"wrote {path} ({os.path.getsize(path) / 1e3:.0f} kB) loss={out['loss']:.6f}")
 
 
 def _grads(model, out):
@@ -134,9 +133,8 @@ def make_variant(name, caption, utils):
     loss.backward()
     out = {"loss": np.float64(loss.item()), "logits": logits.detach().numpy()}
     _grads(model, out)
-    path = os.path.join(HERE, f"{name}.npz")
-    np.savez_compressed(path, **out)
-    print(f"wrote {path} ({os.path.getsize(path) / 1e3:.0f} kB) loss={out['loss']:.6f}")
+    for path in save_golden(name, out):    # kept under 1 MiB per file (tests.helpers)
+        print(f"wrote {path} ({os.path.getsize(path) / 1e3:.0f} kB) loss={out['loss']:.6f}")
 
 
 def make_f2(ct_module):

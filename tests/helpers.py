@@ -1,7 +1,58 @@
 """Shared configs for parity tests (model configs of SURVEY.md §8 and micro variants)."""
 import copy
+import glob
+import os
 
 from retr_amd.configuration import Config
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN_MAX_BYTES = 1 << 20          # no committed fixture file is larger
+
+
+class Golden(dict):
+    """The arrays of one golden case by name (the ``in`` / ``[]`` / ``.files`` of an NpzFile)."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_golden(name):
+    """tests/golden/<name>.npz, plus the arrays kept apart in <name>.part<k>.npz to hold every
+    file under GOLDEN_MAX_BYTES: there ``<key>@<k>`` is slice k of ``<key>`` along axis 0."""
+    import numpy as np
+    g = Golden(np.load(os.path.join(GOLDEN_DIR, f"{name}.npz")))
+    pieces = {}
+    for path in glob.glob(os.path.join(GOLDEN_DIR, f"{name}.part*.npz")):
+        for key, v in np.load(path).items():
+            base, k = key.rsplit("@", 1)
+            pieces.setdefault(base, {})[int(k)] = v
+    for base, d in pieces.items():
+        assert base not in g and sorted(d) == list(range(len(d))), (name, base, sorted(d))
+        g[base] = np.concatenate([d[k] for k in range(len(d))], axis=0)
+    return g
+
+
+def save_golden(name, arrays):
+    """Write what load_golden reads: one compressed npz, and when that would be larger than
+    GOLDEN_MAX_BYTES its largest array moves out, one axis-0 slice per <name>.part<k>.npz."""
+    import numpy as np
+    arrays = dict(arrays)
+    main = os.path.join(GOLDEN_DIR, f"{name}.npz")
+    for old in glob.glob(os.path.join(GOLDEN_DIR, f"{name}.part*.npz")):
+        os.remove(old)
+    np.savez_compressed(main, **arrays)
+    paths = [main]
+    if os.path.getsize(main) > GOLDEN_MAX_BYTES:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        v = arrays.pop(big)
+        np.savez_compressed(main, **arrays)
+        for k in range(v.shape[0]):
+            paths.append(os.path.join(GOLDEN_DIR, f"{name}.part{k}.npz"))
+            np.savez_compressed(paths[-1], **{f"{big}@{k}": v[k:k + 1]})
+    for path in paths:
+        assert os.path.getsize(path) <= GOLDEN_MAX_BYTES, (path, os.path.getsize(path))
+    return paths
 
 
 def make_config(backbone="ResNet18", dilation=False, hidden=64, layers=(1, 1), vocab=1000,

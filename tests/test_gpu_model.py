@@ -131,10 +131,9 @@ def test_bf16_training_step_runs():
 @pytest.mark.parametrize("case", list(PARITY_CASES))
 def test_hip_path_matches_reference_goldens(case):
     """Directly against the vectors the reference produced (tests/golden/*.npz)."""
-    import os
     import numpy as np
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
-                             f"{case}.npz"))
+    from tests.helpers import load_golden
+    g = load_golden(case)
     cfg, model, crit, sd, images, mask, caps, cap_mask = _setup(case)
     model.train()
     out = model(NestedTensor(images.to(DEV), mask.to(DEV)), caps[:, :-1].to(DEV),

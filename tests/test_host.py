@@ -170,3 +170,50 @@ def test_kernel_family_classifier_covers_current_kernel_names():
     assert family_of_symbol("retr::gemm_short_kernel<1, 32, 64, 4, x>(...)") == "linear_dgrad"
     assert family_of_symbol("conv_wgrad_group_kernel<1, 8, 128>") == "conv_wgrad"
     assert family_of_symbol("adamw_update_kernel<true>") is None
+
+
+def test_bench_plain_run_leaves_the_extras_to_full():
+    """A plain ``bench.py --gpus 1 --steps K --warmup W`` times its K steps and nothing else:
+    the per-kernel probe, the decode block and the CPU baselines run under ``--full`` only, and
+    asking a plain run for the probe is an error, not a silently empty answer."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full) == (7, 2, False)
+    assert a.probe_steps == 0 and a.no_decode and a.no_cpu_baseline and not a.dump_outputs
+    f = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full"])
+    assert f.full and f.probe_steps == 2 and not f.no_decode and not f.no_cpu_baseline
+    f = bench.parse_args(["--full", "--workload", "cfg4", "--probe-steps", "1"])
+    assert f.probe_steps == 1 and f.no_decode and (f.size, f.batch) == (800, 8)
+    assert bench.parse_args(["--probe-steps", "0", "--no-decode"]).probe_steps == 0
+    for bad in (["--probe-detail", "t.txt"], ["--probe-steps", "1"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_bench_dump_outputs_writes_loss_and_parameter_norms(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files and nothing else: the step's loss and
+    the L2 norm of every trainable parameter (frozen ones left out), the same on every call and
+    following the parameters when they change."""
+    import numpy as np
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Linear(5, 3))
+    model[1].bias.requires_grad_(False)
+    loss = torch.tensor(1.25)
+
+    def dump(sub):
+        names = bench.dump_outputs(str(tmp_path / sub), loss, model)
+        assert sorted(os.listdir(tmp_path / sub)) == sorted(n + ".npy" for n in names)
+        return {n: np.load(tmp_path / sub / (n + ".npy")) for n in names}
+
+    d = dump("a")
+    assert d["loss"].dtype == np.float32 and d["loss"].tolist() == [1.25]
+    assert d["param_norms"].dtype == np.float64 and d["param_norms"].shape == (3,)
+    want = [p.detach().double().norm().item() for p in model.parameters() if p.requires_grad]
+    np.testing.assert_allclose(d["param_norms"], want, rtol=1e-15)
+    np.testing.assert_array_equal(dump("b")["param_norms"], d["param_norms"])
+    with torch.no_grad():
+        model[0].weight.add_(1.0)
+    c = dump("c")["param_norms"]
+    assert c[0] != d["param_norms"][0]
+    np.testing.assert_array_equal(c[1:], d["param_norms"][1:])

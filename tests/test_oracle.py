@@ -9,8 +9,8 @@ import torch
 from oracle import model as orc
 from retr_amd.models.caption import build_model
 from retr_amd.synthetic import synthetic_captions, synthetic_images, synthetic_state_dict
-from tests.helpers import (F2_CASE, PARITY_CASES, VARIANT_CASES, f2_inputs, make_config,
-                           variant_config, variant_inputs)
+from tests.helpers import (F2_CASE, PARITY_CASES, VARIANT_CASES, f2_inputs, load_golden,
+                           make_config, variant_config, variant_inputs)
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -28,7 +28,7 @@ def _case(name):
 
 @pytest.mark.parametrize("name", list(PARITY_CASES))
 def test_oracle_forward_backward_matches_reference(name):
-    g = np.load(os.path.join(GOLD, f"{name}.npz"))
+    g = load_golden(name)
     cfg, sd, images, mask, caps, cap_mask, trainable = _case(name)
     assert list(g["grad_names"]) == trainable          # same freeze policy as the reference
     sdo = {k: (v.clone().requires_grad_(True) if k in trainable else v) for k, v in sd.items()}
@@ -54,7 +54,7 @@ def test_oracle_forward_backward_matches_reference(name):
 
 @pytest.mark.parametrize("name", [n for n in PARITY_CASES if n.startswith("micro")])
 def test_oracle_attention_and_greedy_match_reference(name):
-    g = np.load(os.path.join(GOLD, f"{name}.npz"))
+    g = load_golden(name)
     cfg, sd, images, mask, caps, cap_mask, _ = _case(name)
     with torch.no_grad():
         _, att = orc.caption_forward(sd, cfg, images, mask, caps[:, :-1], cap_mask[:, :-1],
@@ -133,7 +133,7 @@ def test_oracle_f2_transformer_matches_reference():
 def test_oracle_beam1_is_reference_greedy(name):
     """The beam-search restatement (no reference implementation exists) is anchored to the
     reference through beam_size=1 == eval_utils/decode.py greedy, on the reference's own ids."""
-    g = np.load(os.path.join(GOLD, f"{name}.npz"))
+    g = load_golden(name)
     cfg, sd, images, mask, caps, cap_mask, _ = _case(name)
     T = cfg.max_position_embeddings
     for i, eos in enumerate(g["greedy_eos"]):

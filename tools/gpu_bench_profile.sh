@@ -7,11 +7,11 @@ TAG=${1:-r2}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-timeout -k 10 560 python bench.py --steps 20 --warmup 5 --probe-detail $OUT/probe_shapes.txt \
+timeout -k 10 560 python bench.py --full --steps 20 --warmup 5 --probe-detail $OUT/probe_shapes.txt \
   > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed $?"; exit 1; }
 echo "bench done"; tail -c 600 $OUT/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run -- \
-  python bench.py --steps 6 --warmup 2 --no-decode --no-cpu-baseline --probe-steps 1 \
+  python bench.py --full --steps 6 --warmup 2 --no-decode --no-cpu-baseline --probe-steps 1 \
   > $OUT/trace_bench.json 2> $OUT/trace.err || { echo "trace failed $?"; exit 1; }
 echo "trace done"
 timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- \

@@ -9,14 +9,14 @@ TAG=${1:-r5}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 420 python bench.py --steps 20 --warmup 5 --probe-detail $OUT/probe_shapes.txt \
+timeout -k 10 420 python bench.py --full --steps 20 --warmup 5 --probe-detail $OUT/probe_shapes.txt \
   > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed $?"; exit 1; }
 echo "bench done"; tail -c 300 $OUT/bench.json
-timeout -k 10 300 python bench.py --workload cfg4 --steps 10 --warmup 3 --no-decode \
+timeout -k 10 300 python bench.py --full --workload cfg4 --steps 10 --warmup 3 --no-decode \
   > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err || { echo "cfg4 failed $?"; exit 1; }
 echo "cfg4 done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run -- \
-  python3 bench.py --steps 6 --warmup 2 --no-decode --no-cpu-baseline --probe-steps 1 \
+  python3 bench.py --full --steps 6 --warmup 2 --no-decode --no-cpu-baseline --probe-steps 1 \
   > $OUT/trace_bench.json 2> $OUT/trace.err || { echo "trace failed $?"; exit 1; }
 echo "trace done"
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- \

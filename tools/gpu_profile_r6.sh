@@ -51,14 +51,14 @@ if [ "$PHASE" != run ]; then
   pmc cfg4
 fi
 [ "$PHASE" = pmc ] && exit 0
-step bench 420 python bench.py --steps 20 --warmup 5 --probe-detail $OUT/probe_shapes.txt
+step bench 420 python bench.py --full --steps 20 --warmup 5 --probe-detail $OUT/probe_shapes.txt
 cp $OUT/bench.log $OUT/bench.json
 echo "bench done"; grep -o '"value": [0-9.]*' $OUT/bench.json | head -3
-step bench_cfg4 300 python bench.py --workload cfg4 --steps 10 --warmup 3 --no-decode
+step bench_cfg4 300 python bench.py --full --workload cfg4 --steps 10 --warmup 3 --no-decode
 cp $OUT/bench_cfg4.log $OUT/bench_cfg4.json
 echo "cfg4 done"
 step trace 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run -- \
-  python3 bench.py --steps 6 --warmup 2 --no-decode --no-cpu-baseline --probe-steps 1
+  python3 bench.py --full --steps 6 --warmup 2 --no-decode --no-cpu-baseline --probe-steps 1
 echo "trace done"
 step dec 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/dec -o run -- \
   python3 tools/decode_prof.py --reps 2
