@@ -546,6 +546,43 @@ int retr_ce_fwd_bwd(int dtype, const void* logits, long ld, int M, int V,
 int retr_ce_bwd_rescale(int dtype, const void* logits, long ld, int M, int V,
                         const long long* targets, const float* lse, const float* dloss,
                         float inv_count, void* dlogits, long lddl, void* stream);
+/* The same loss with nn.CrossEntropyLoss's options (additive: the four entry points above are
+   untouched).  For a row with target t, eps = label_smoothing, lse = logsumexp(x[0..V)):
+     loss_rows[row] = (1-eps)(lse - x[t]) + eps (lse - mean_j x[j]),  0 when t == ignore_index;
+     dlogits[row][j] = g (softmax_j - (1-eps)[j == t] - eps/V), a zero row when t == ignore_index,
+     zeros in columns [V, lddl).
+   ignore_index is any int64 (negative, or a class id such as the pad id).  A target neither
+   ignored nor in [0, V) is never used as an index: that row's loss is NaN and its gradient has
+   no one-hot term.
+   retr_ce_count writes N_valid = #{t != ignore_index} as a float to the device scalar `denom`.
+   `denom` of the other calls selects the reduction: non-NULL = mean, *loss = sum(loss_rows) /
+   *denom (NaN when N_valid is 0) and g carries 1 / *denom, read on the device, so
+   retr_ce_count precedes them on the same stream (and a captured graph follows the targets it
+   is replayed on); NULL = sum.  loss == NULL skips the reduction (reduction 'none').
+   retr_ce_bwd_opt: g = dloss[row * dloss_stride] (/ *denom), dloss_stride 0 for a scalar
+   upstream gradient, 1 for one per row (reduction 'none', denom NULL).
+   retr_ce_fwd_bwd_opt / retr_ce_bwd_rescale_opt: the one-pass training form under
+   retr_ce_fwd_bwd's constraints (bf16, ld % 8 == 0, lddl % 8 == 0, 16-byte aligned,
+   lddl <= 32768): dlogits as for dloss = 1, rewritten by the rescale call only when
+   *dloss != 1.  A row whose target is ignored is not read. */
+int retr_ce_count(int M, const long long* targets, long long ignore_index, float* denom,
+                  void* stream);
+int retr_ce_fwd_opt(int dtype, const void* logits, long ld, int M, int V,
+                    const long long* targets, long long ignore_index, float label_smoothing,
+                    float* lse, float* loss_rows, float* loss, const float* denom,
+                    void* stream);
+int retr_ce_bwd_opt(int dtype, const void* logits, long ld, int M, int V,
+                    const long long* targets, long long ignore_index, float label_smoothing,
+                    const float* lse, const float* dloss, long dloss_stride, const float* denom,
+                    void* dlogits, long lddl, void* stream);
+int retr_ce_fwd_bwd_opt(int dtype, const void* logits, long ld, int M, int V,
+                        const long long* targets, long long ignore_index, float label_smoothing,
+                        float* lse, float* loss_rows, float* loss, const float* denom,
+                        void* dlogits, long lddl, void* stream);
+int retr_ce_bwd_rescale_opt(int dtype, const void* logits, long ld, int M, int V,
+                            const long long* targets, long long ignore_index,
+                            float label_smoothing, const float* lse, const float* dloss,
+                            const float* denom, void* dlogits, long lddl, void* stream);
 int retr_argmax_rows(int dtype, const void* x, long ld, int M, int V, long long* out,
                      void* stream);
 /* the same first-index argmax for few long rows (decode logits): 16 segments per row in

@@ -25,6 +25,7 @@ TUNE_COUNT = 40          # include/retr_hip.h RETR_TUNE_COUNT
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_long
+_LL = ctypes.c_longlong
 _F = ctypes.c_float
 _D = ctypes.c_double
 _U64 = ctypes.c_ulonglong
@@ -192,6 +193,11 @@ _SIGS = {
     "retr_ce_bwd": [_I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _P],
     "retr_ce_fwd_bwd": [_I, _P, _L, _I, _I, _P, _P, _P, _P, _F, _P, _L, _P],
     "retr_ce_bwd_rescale": [_I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _P],
+    "retr_ce_count": [_I, _P, _LL, _P, _P],
+    "retr_ce_fwd_opt": [_I, _P, _L, _I, _I, _P, _LL, _F, _P, _P, _P, _P, _P],
+    "retr_ce_bwd_opt": [_I, _P, _L, _I, _I, _P, _LL, _F, _P, _P, _L, _P, _P, _L, _P],
+    "retr_ce_fwd_bwd_opt": [_I, _P, _L, _I, _I, _P, _LL, _F, _P, _P, _P, _P, _P, _L, _P],
+    "retr_ce_bwd_rescale_opt": [_I, _P, _L, _I, _I, _P, _LL, _F, _P, _P, _P, _P, _L, _P],
     "retr_argmax_rows": [_I, _P, _L, _I, _I, _P, _P],
     "retr_argmax_workspace": [_I],
     "retr_argmax_rows_ws": [_I, _P, _L, _I, _I, _P, _P, _P],

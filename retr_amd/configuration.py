@@ -6,6 +6,8 @@
 * ``grad_bucket_mb``: data-parallel gradient bucket size.
 * ``deterministic``: fixed-order reductions everywhere (no split-K fp32 atomics), so two runs
   on the same inputs give bitwise-equal gradients and weights (``retr_set_deterministic``).
+* ``label_smoothing`` / ``loss_ignore_pad``: options of the criterion ``build_model`` returns
+  (``loss_ignore_pad`` averages the loss over the rows whose target is not ``pad_token_id``).
 """
 from os.path import join
 
@@ -54,6 +56,9 @@ class Config(object):
         self.dtype = "bf16"
         self.grad_bucket_mb = 64
         self.deterministic = False
+        # criterion options (defaults = the reference's CrossEntropyLoss())
+        self.label_smoothing = 0.0
+        self.loss_ignore_pad = False
 
 
 def compute_dtype(config):

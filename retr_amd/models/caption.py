@@ -208,15 +208,30 @@ class CaptionGlobalLoc(_ConcatMixin, Caption):
 
 
 class CrossEntropyLoss(nn.CrossEntropyLoss):
-    """``torch.nn.CrossEntropyLoss()`` semantics (mean, no ignore_index hit for pad id 0) on the
-    fused HIP kernel; called exactly as engine.py:71 does: criterion(out.permute(0,2,1), tgt)."""
+    """``torch.nn.CrossEntropyLoss`` on the HIP kernels; called exactly as engine.py:71 does:
+    criterion(out.permute(0,2,1), tgt).
+
+    The default construction ``CrossEntropyLoss()`` (ignore_index -100, label_smoothing 0,
+    reduction 'mean') is the reference's criterion and keeps its kernels: the mean runs over
+    all B*T rows (pad id 0 included), and a target equal to -100 is NOT honoured there (every
+    target must be a class id).  Any other ``ignore_index`` (negative or a class id such as the
+    pad id), ``label_smoothing`` or ``reduction`` ('mean' over the rows not ignored, 'sum',
+    'none' -> [B, T]) runs the option kernels with torch's semantics, -100 included.  Class
+    ``weight`` is not supported."""
 
     def forward(self, input, target):
         from .. import ops
-        if input.dim() != 3 or self.reduction != "mean" or self.weight is not None \
-                or self.label_smoothing != 0.0:
-            raise NotImplementedError("only the reference's CrossEntropyLoss() call is supported")
-        return ops.cross_entropy(input, target)
+        if input.dim() != 3:
+            raise NotImplementedError("CrossEntropyLoss: logits [B, V, T] and targets [B, T] "
+                                      "only (the reference's call)")
+        if self.weight is not None:
+            raise NotImplementedError("CrossEntropyLoss: class weights are not supported")
+        if self.ignore_index == -100 and self.label_smoothing == 0.0 \
+                and self.reduction == "mean":
+            return ops.cross_entropy(input, target)
+        return ops.cross_entropy(input, target, ignore_index=self.ignore_index,
+                                 label_smoothing=self.label_smoothing,
+                                 reduction=self.reduction)
 
 
 def build_model(config):
@@ -239,5 +254,8 @@ def build_model(config):
         from .. import ops
         ops.set_deterministic(True)
     print(f"Built {model.__class__.__name__} model with {transformer.__class__.__name__}")
-    criterion = CrossEntropyLoss()
+    # defaults (loss_ignore_pad False, label_smoothing 0): the reference's CrossEntropyLoss()
+    ignore = config.pad_token_id if getattr(config, "loss_ignore_pad", False) else -100
+    criterion = CrossEntropyLoss(ignore_index=ignore,
+                                 label_smoothing=getattr(config, "label_smoothing", 0.0))
     return model, criterion

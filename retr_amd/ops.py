@@ -10,7 +10,8 @@ reference computes as separate PyTorch ops:
 * ``embed_ln``        DecoderEmbeddings                                          (:100-129)
 * ``linear``          input_proj (1x1 conv) and plain linears
 * ``mlp_head``        MLP(C, 512, V, 3)                          models/caption.py:161-174
-* ``cross_entropy``   CrossEntropyLoss (mean, no ignore_index)  caption.py:210 / engine.py:71
+* ``cross_entropy``   CrossEntropyLoss (mean, no ignore_index)  caption.py:210 / engine.py:71;
+                      with ignore_index / label_smoothing / reduction: the retr_ce_*_opt kernels
 * ``backbone``        ResNet body (NHWC implicit-GEMM convs, FrozenBN folded) backbone.py:41-77
 
 Tensors of the residual stream are fp32; GEMM operands are the compute dtype (bf16 or fp32).
@@ -1612,8 +1613,83 @@ class _CrossEntropy(torch.autograd.Function):
         return dl[:, :V].view(B, T, V).permute(0, 2, 1), None
 
 
-def cross_entropy(x, target):
-    return _CrossEntropy.apply(x, target)
+class _CrossEntropyOpt(torch.autograd.Function):
+    """Cross entropy with ignore_index / label smoothing / reduction (retr_ce_*_opt).  The
+    mean's denominator N_valid is counted on the device (retr_ce_count) and read there by the
+    loss and gradient kernels: no host sync, no data-dependent allocation, capturable."""
+
+    @staticmethod
+    def forward(ctx, x, target, ignore_index, eps, reduction):
+        # x: [B, V, T] (permuted view of [B, T, V] logits whose rows may be padded)
+        _lib.require_device(x, target)
+        B, V, T = x.shape
+        if x.stride(1) == 1 and x.stride(0) == T * x.stride(2):
+            base, ld = x, x.stride(2)
+        else:
+            base = x.permute(0, 2, 1).contiguous()
+            ld = V
+        M = B * T
+        dev = x.device
+        tgt = target.reshape(M).contiguous()
+        lse = torch.empty(M, dtype=torch.float32, device=dev)
+        rows = torch.empty(M, dtype=torch.float32, device=dev)
+        loss = denom = None
+        if reduction != "none":
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+        if reduction == "mean":
+            denom = torch.empty((), dtype=torch.float32, device=dev)
+            call("retr_ce_count", M, ptr(tgt), ignore_index, ptr(denom), _st())
+        Vp = _round_up(V, 64)
+        ctx.dl = None
+        if (ctx.needs_input_grad[0] and base.dtype == torch.bfloat16 and ld % 8 == 0
+                and Vp <= 32768 and FUSED_CE and _TRAIN_STEP > 0 and reduction != "none"):
+            # training: the gradient for dloss = 1 comes out of the same pass over the logits
+            ctx.dl = torch.empty(M, Vp, dtype=base.dtype, device=dev)
+            call("retr_ce_fwd_bwd_opt", dcode(base.dtype), ptr(base), ld, M, V, ptr(tgt),
+                 ignore_index, eps, ptr(lse), ptr(rows), ptr(loss), ptr(denom), ptr(ctx.dl), Vp,
+                 _st())
+        else:
+            call("retr_ce_fwd_opt", dcode(base.dtype), ptr(base), ld, M, V, ptr(tgt),
+                 ignore_index, eps, ptr(lse), ptr(rows), ptr(loss), ptr(denom), _st())
+        ctx.save_for_backward(base, tgt, lse, denom)
+        ctx.cfg = (B, V, T, ld, ignore_index, eps, reduction)
+        return rows.view(B, T) if reduction == "none" else loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        base, tgt, lse, denom = ctx.saved_tensors
+        B, V, T, ld, ignore_index, eps, reduction = ctx.cfg
+        M = B * T
+        Vp = _round_up(V, 64)
+        per_row = reduction == "none"
+        dloss = dloss.reshape(M if per_row else 1).float().contiguous()
+        dl = ctx.dl
+        ctx.dl = None
+        if dl is not None:
+            call("retr_ce_bwd_rescale_opt", dcode(base.dtype), ptr(base), ld, M, V, ptr(tgt),
+                 ignore_index, eps, ptr(lse), ptr(dloss), ptr(denom), ptr(dl), Vp, _st())
+        else:
+            dl = torch.empty(M, Vp, dtype=base.dtype, device=base.device)
+            call("retr_ce_bwd_opt", dcode(base.dtype), ptr(base), ld, M, V, ptr(tgt),
+                 ignore_index, eps, ptr(lse), ptr(dloss), 1 if per_row else 0, ptr(denom),
+                 ptr(dl), Vp, _st())
+        return dl[:, :V].view(B, T, V).permute(0, 2, 1), None, None, None, None
+
+
+def cross_entropy(x, target, ignore_index=None, label_smoothing=0.0, reduction="mean"):
+    """Cross entropy of logits ``x`` [B, V, T] (the permuted [B, T, V] view) against ``target``
+    [B, T].  With every default this is the reference's bare ``CrossEntropyLoss()`` path
+    (retr_ce_fwd / retr_ce_fwd_bwd: mean over all B*T rows, no target is ignored).  Any option
+    selects the retr_ce_*_opt kernels with torch's semantics; there ``ignore_index=None``
+    means torch's default -100."""
+    if ignore_index is None and label_smoothing == 0.0 and reduction == "mean":
+        return _CrossEntropy.apply(x, target)
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"{reduction} is not a valid value for reduction")
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
+    return _CrossEntropyOpt.apply(x, target, -100 if ignore_index is None else int(ignore_index),
+                                  float(label_smoothing), reduction)
 
 
 def argmax_rows(x2d):
