@@ -1,15 +1,22 @@
 """ctypes binding of ``libretr_hip.so`` (the gfx950 kernels; C-ABI in ``include/retr_hip.h``).
 
+The header is the only place where a signature, a struct layout or a tuning-knob number is
+written: this module parses it at import and derives every ``argtypes`` / ``restype``, the
+``ctypes.Structure`` classes and the ``TUNE`` name table from it.
+
 The product path has no fallback: if the library is missing or a CUDA/HIP device is absent,
 every op raises.  Build the library with ``make`` (or ``__graft_entry__.build()``).
 """
+import contextlib
 import ctypes
 import os
+import re
 import warnings
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "retr_hip.h")
 LIB_PATH = os.path.join(_HERE, "libretr_hip.so")
 # A/B measurements only (tools/*_micro.py, tools/ab_step.py): time a baseline build of the same
 # C-ABI.  Never silent: a stray setting would swap every kernel of the process.
@@ -19,238 +26,120 @@ if os.environ.get("RETR_AB_LIB"):
     print(f"retr_amd: RETR_AB_LIB is set -- loading kernels from {LIB_PATH} instead of the "
           f"in-tree libretr_hip.so (A/B tooling only)", file=_sys.stderr)
 
-F32, BF16 = 0, 1
-TUNE_COUNT = 40          # include/retr_hip.h RETR_TUNE_COUNT
-
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_L = ctypes.c_long
-_LL = ctypes.c_longlong
-_F = ctypes.c_float
-_D = ctypes.c_double
-_U64 = ctypes.c_ulonglong
-_SZ = ctypes.c_size_t
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong,
+            "unsigned long long": ctypes.c_ulonglong, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+_POINTEES = set(_SCALARS) | {"void", "char", "unsigned char"}      # behind a plain void*
+_DECLARATOR = re.compile(r"(.+?)([\s*]+)(\w+)\s*(?:\[\s*(\d+)\s*\])?")
+_PROTOTYPE = re.compile(r"([\w\s*]+?)\b(\w+)\s*\(([^()]*)\)")
 
 
-
-class LinearFwdDesc(ctypes.Structure):
-    """retr_linear_fwd_desc (include/retr_hip.h)"""
-    _fields_ = [("x", _P), ("ldx", _L), ("w", _P), ("ldw", _L), ("bias", _P), ("y", _P),
-                ("ldy", _L), ("residual", _P), ("ldr", _L), ("drop_p", _F), ("seed", _U64),
-                ("M", _I), ("N", _I), ("K", _I), ("relu", _I)]
-
-
-class LinearDgradDesc(ctypes.Structure):
-    """retr_linear_dgrad_desc"""
-    _fields_ = [("dy", _P), ("lddy", _L), ("w", _P), ("ldw", _L), ("dx", _P), ("lddx", _L),
-                ("addend", _P), ("lda", _L), ("gate", _P), ("ldg", _L), ("M", _I), ("N", _I),
-                ("K", _I), ("pad", _I)]
-
-
-class LinearWgradDesc(ctypes.Structure):
-    """retr_linear_wgrad_desc"""
-    _fields_ = [("dy", _P), ("lddy", _L), ("x", _P), ("ldx", _L), ("dw", _P), ("lddw", _L),
-                ("db", _P), ("M", _I), ("N", _I), ("K", _I), ("accumulate", _I)]
+def _ctype(spelling, structs, where, returned=False):
+    """The ctypes type of a C type as the header spells it ('const float*', 'long', ...)."""
+    base = " ".join(w for w in spelling.replace("*", " ").split() if w != "const")
+    stars = spelling.count("*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 0 and base == "void" and returned:
+        return None
+    if stars == 1 and base == "char" and returned:
+        return ctypes.c_char_p
+    if stars == 1 and base in structs and not returned:
+        return ctypes.POINTER(structs[base])
+    if stars >= 1 and base in _POINTEES and not returned:
+        return ctypes.c_void_p
+    raise RuntimeError(f"retr_hip.h: unknown C type {spelling.strip()!r} in `{where}`")
 
 
-class ConvWgradDesc(ctypes.Structure):
-    """retr_conv_wgrad_desc"""
-    _fields_ = [("dy", _P), ("x", _P), ("ws", _P), ("Nb", _I), ("H", _I), ("W", _I), ("C", _I),
-                ("Co", _I), ("KH", _I), ("KW", _I), ("stride", _I), ("pad", _I), ("dil", _I),
-                ("splits", _I), ("kind", _I)]
+def _declarations(decl, structs, where):
+    """[(name, ctypes type)] of one declaration: 'int M, N', 'const float *w, *bn_w',
+    'float f[3]' or a single function parameter."""
+    out, base = [], ""
+    for piece in decl.split(","):             # later declarators share the first one's base type
+        m = _DECLARATOR.fullmatch(f"{base} {piece.strip()}".strip())
+        if m is None:
+            raise RuntimeError(f"retr_hip.h: cannot parse `{where}`")
+        base = m.group(1)
+        t = _ctype(base + m.group(2), structs, where)
+        out.append((m.group(3), t * int(m.group(4)) if m.group(4) else t))
+    return out
 
 
-class ConvUnpackDesc(ctypes.Structure):
-    """retr_conv_unpack_desc"""
-    _fields_ = [("ws", _P), ("scale", _P), ("grad", _P), ("Co", _I), ("Ci", _I), ("Cp", _I),
-                ("KH", _I), ("KW", _I), ("splits", _I), ("accumulate", _I), ("pad", _I)]
+def parse_header(src):
+    """(functions, structs, constants) of a C header in the style of include/retr_hip.h.
+
+    functions: name -> (restype, [(parameter name, ctypes type)]) in declaration order;
+    structs: typedef name -> ctypes.Structure subclass; constants: enum members and integer
+    #defines.  Text that is none of these is an error, as is a type outside the table above:
+    nothing is skipped and nothing defaults to int."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", src, flags=re.S)
+    constants = {m.group(1): int(m.group(2), 0) for m in re.finditer(
+        r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", src, re.M)}
+    src = re.sub(r"^[ \t]*#.*$", " ", src, flags=re.M)
+    src = re.sub(r'extern\s+"C"\s*\{', " ", src)
+    functions, structs = {}, {}
+
+    def enum(m):
+        value = -1
+        for item in filter(str.strip, m.group(1).split(",")):
+            name, _, given = item.partition("=")
+            value = int(given, 0) if given.strip() else value + 1
+            constants[name.strip()] = value
+        return " "
+
+    def struct(m):
+        name, fields = m.group(2), []
+        for decl in filter(str.strip, m.group(1).split(";")):
+            fields += _declarations(decl, structs, f"{name}: {' '.join(decl.split())}")
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+        return " "
+
+    src = re.sub(r"\benum\s*\{([^{}]*)\}\s*;", enum, src)
+    src = re.sub(r"\btypedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, src)
+    *prototypes, tail = src.split(";")            # what is left: `ret name(params);` ...
+    if tail.strip() not in ("", "}"):             # ... and the closing brace of extern "C"
+        prototypes.append(tail)
+    for text in prototypes:
+        where = " ".join(text.split())
+        m = _PROTOTYPE.fullmatch(where)
+        if m is None:
+            raise RuntimeError(f"retr_hip.h: cannot parse the declaration `{where[:200]}`")
+        args = []
+        if m.group(3).strip() != "void":
+            for p in m.group(3).split(","):
+                args += _declarations(p, structs, where)
+        functions[m.group(2)] = (_ctype(m.group(1), structs, where, returned=True), args)
+    return functions, structs, constants
 
 
-class PosItem(ctypes.Structure):
-    """retr_pos_item"""
-    _fields_ = [("d", _P), ("ld", _L), ("M", _I), ("pad", _I)]
+def _read_header():
+    try:
+        with open(HEADER_PATH, encoding="utf-8") as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise RuntimeError(f"retr_amd: the C-ABI header {HEADER_PATH} cannot be read ({e}); the "
+                           "binding is derived from it") from e
 
 
-class LnOut(ctypes.Structure):
-    """retr_ln_out"""
-    _fields_ = [("gamma", _P), ("beta", _P), ("eps", _F), ("y_bf16", _I), ("y", _P), ("y2", _P),
-                ("ldy", _L), ("pos", _P), ("period", _I), ("mean", _P), ("rstd", _P)]
+FUNCTIONS, STRUCTS, CONSTANTS = _read_header()
 
+F32, BF16 = CONSTANTS["RETR_DTYPE_F32"], CONSTANTS["RETR_DTYPE_BF16"]
+TUNE_COUNT = CONSTANTS["RETR_TUNE_COUNT"]
+# tuning knobs by name: TUNE["ATTN_MODE"] == 5
+TUNE = {k[len("RETR_TUNE_"):]: v for k, v in CONSTANTS.items()
+        if k.startswith("RETR_TUNE_") and k != "RETR_TUNE_COUNT"}
 
-class ConvPackDesc(ctypes.Structure):
-    """retr_conv_pack_desc"""
-    _fields_ = [("w", _P), ("bn_w", _P), ("bn_b", _P), ("bn_rm", _P), ("bn_rv", _P),
-                ("conv_bias", _P), ("w_out", _P), ("wt_out", _P), ("bias_out", _P),
-                ("scale_out", _P), ("Co", _I), ("Ci", _I), ("KH", _I), ("KW", _I), ("Cp", _I),
-                ("pad", _I)]
-
-
-class CatRowsDesc(ctypes.Structure):
-    """retr_cat_rows_desc"""
-    _fields_ = [("a", _P), ("b", _P), ("dst", _P), ("bias_a", _P), ("bias_b", _P),
-                ("bias_dst", _P), ("rows", _I), ("ka", _I), ("kb", _I)]
-
-
-class SlabSumDesc(ctypes.Structure):
-    """retr_slab_sum_desc"""
-    _fields_ = [("parts", _P), ("stride", _L), ("nparts", _I), ("cols", _I), ("dst", _P),
-                ("accumulate", _I)]
-
-
-_PFD = ctypes.POINTER(LinearFwdDesc)
-_PDD = ctypes.POINTER(LinearDgradDesc)
-_PWD = ctypes.POINTER(LinearWgradDesc)
-
-# name -> argtypes (all functions return int unless listed in _RESTYPE)
-_SIGS = {
-    "retr_abi_version": [],
-    "retr_last_error": [],
-    "retr_set_seed_base": [_P],
-    "retr_seed_bump": [_P, _U64, _P],
-    "retr_spin_us": [_F, _P],
-    "retr_linear_fwd": [_I, _P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _P, _L, _F, _U64, _P],
-    "retr_linear_dgrad": [_I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _I, _L, _P, _L, _I,
-                          _P],
-    "retr_transpose_cast": [_I, _P, _P, _I, _I, _I, _P],
-    "retr_linear_splits": [_I, _I, _I, _I],
-    "retr_ffn_splits": [_I, _I, _I],
-    "retr_ffn_fwd": [_P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P, _L, _I, _I, _I, _F, _U64, _P,
-                     _I, _P],
-    "retr_ffn_bwd_data": [_P, _L, _P, _P, _L, _P, _P, _L, _P, _L, _I, _I, _I, _P, _I, _P],
-    "retr_linear_fwd_splitk": [_I, _P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _P, _L, _F,
-                               _U64, _P, _I, _P],
-    "retr_linear_fwd_splitk_ln": [_I, _P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _P, _L, _F,
-                                  _U64, _P, _I, ctypes.POINTER(LnOut), _P],
-    "retr_linear_dgrad_splitk": [_I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _I, _L, _P, _L,
-                                 _I, _P, _I, _P],
-    "retr_linear_dgrad_slabs": [_I, _P, _L, _P, _L, _I, _I, _I, _I, _P, _I, _P],
-    "retr_linear_wgrad": [_I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _I, _P],
-    "retr_bias_grad": [_I, _P, _L, _I, _I, _P, _P],
-    "retr_linear_fwd_group": [_I, _I, _I, _PFD, _P],
-    "retr_linear_dgrad_group": [_I, _I, _I, _I, _I, _PDD, _P],
-    "retr_linear_wgrad_group_workspace": [_I, _PWD],
-    "retr_linear_wgrad_group": [_I, _I, _PWD, _P, _P],
-    "retr_linear_wgrad_group2": [_I, _I, _PWD, _P, _I, ctypes.POINTER(SlabSumDesc), _P],
-    "retr_linear_wgrad_batch_table_bytes": [_I, _I],
-    "retr_linear_wgrad_batch": [_I, _PWD, _I, ctypes.POINTER(SlabSumDesc), _P, _SZ, _P],
-    "retr_conv_pack": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "retr_conv_pack_group": [_I, _I, ctypes.POINTER(ConvPackDesc), _P],
-    "retr_cat_rows_group": [_I, ctypes.POINTER(CatRowsDesc), _P],
-    "retr_conv2d_fwd": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "retr_conv2d_dgrad": [_I, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "retr_conv2d_wgrad": [_I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P],
-    "retr_conv_wgrad_unpack": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "retr_conv2d_wgrad_group_table_bytes": [_I],
-    "retr_conv2d_wgrad_group_plan": [_I, _I, ctypes.POINTER(ConvWgradDesc)],
-    "retr_conv2d_wgrad_group": [_I, _I, ctypes.POINTER(ConvWgradDesc), _P, _SZ, _P],
-    "retr_conv_wgrad_unpack_group_table_bytes": [_I],
-    "retr_conv_wgrad_unpack_group": [_I, ctypes.POINTER(ConvUnpackDesc), _P, _SZ, _P],
-    "retr_conv2d_wgrad_splits": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I],
-    "retr_nchw_to_nhwc": [_I, _P, _P, _I, _I, _I, _I, _I, _P],
-    "retr_nchw_to_s2d16": [_P, _P, _I, _I, _I, _I, _P],
-    "retr_pipe_run": [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P],
-    "retr_stem_s2d_weights": [_P, _P, _I, _I, _P],
-    "retr_conv2d_fwd_out": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I,
-                            _I, _I, _P],
-    "retr_bottleneck_s1_fwd": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    "retr_conv1x1_fwd_cat": [_I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I,
-                             _P],
-    "retr_maxpool3x3s2": [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "retr_stem_pool_fwd": [_I, _P, _I, _I, _I, _P, _P, _P, _I, _P],
-    "retr_mask_nearest": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "retr_layernorm_fwd": [_I, _P, _L, _P, _P, _F, _I, _I, _P, _L, _P, _P, _I, _P, _P, _P],
-    "retr_layernorm_bwd": [_I, _P, _P, _L, _P, _L, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P,
-                           _P],
-    "retr_layernorm_bwd_workspace": [_I, _I],
-    "retr_layernorm_bwd2": [_I, _P, _P, _L, _P, _L, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P,
-                            _P, _L, _F, _U64, _P, _P],
-    "retr_layernorm_bwd_slabs": [_P, _I, _P, _L, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P,
-                                 _L, _F, _U64, _P, _P],
-    "retr_embed_ln_fwd": [_P, _I, _I, _I, _P, _P, _P, _P, _F, _F, _U64, _P, _P, _P, _P],
-    "retr_embed_ln_bwd": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _U64, _P, _P, _P, _P, _I,
-                          _P, _P],
-    "retr_embed_ln_bwd_workspace": [_I, _I, _I],
-    "retr_set_deterministic": [_I],
-    "retr_get_deterministic": [],
-    "retr_tune": [_I, _I],
-    "retr_attention_fwd": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _F,
-                           _U64, _P, _P, _P],
-    "retr_attention_bwd": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _L, _P,
-                           _L, _I, _I, _I, _I, _I, _P, _I, _F, _U64, _P, _P],
-    "retr_attention_bwd_workspace": [_I, _I, _I],
-    "retr_attention_fwd_dm": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _F,
-                              _U64, _P, _P, _P, _P],
-    "retr_attention_bwd_dm": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _L,
-                              _P, _L, _I, _I, _I, _I, _I, _P, _I, _F, _U64, _P, _P, _P],
-    "retr_attention_dropout_mask_bytes": [_I, _I, _I, _I],
-    "retr_attention_decode": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I,
-                              _P, _P],
-    "retr_topk_rows": [_I, _P, _L, _I, _I, _I, _P, _P, _P],
-    "retr_beam_select": [_P, _P, _I, _I, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, _P,
-                         _P],
-    "retr_greedy_update": [_P, _I, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, _P],
-    "retr_ce_fwd": [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P],
-    "retr_ce_bwd": [_I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _P],
-    "retr_ce_fwd_bwd": [_I, _P, _L, _I, _I, _P, _P, _P, _P, _F, _P, _L, _P],
-    "retr_ce_bwd_rescale": [_I, _P, _L, _I, _I, _P, _P, _P, _F, _P, _L, _P],
-    "retr_ce_count": [_I, _P, _LL, _P, _P],
-    "retr_ce_fwd_opt": [_I, _P, _L, _I, _I, _P, _LL, _F, _P, _P, _P, _P, _P],
-    "retr_ce_bwd_opt": [_I, _P, _L, _I, _I, _P, _LL, _F, _P, _P, _L, _P, _P, _L, _P],
-    "retr_ce_fwd_bwd_opt": [_I, _P, _L, _I, _I, _P, _LL, _F, _P, _P, _P, _P, _P, _L, _P],
-    "retr_ce_bwd_rescale_opt": [_I, _P, _L, _I, _I, _P, _LL, _F, _P, _P, _P, _P, _L, _P],
-    "retr_argmax_rows": [_I, _P, _L, _I, _I, _P, _P],
-    "retr_argmax_workspace": [_I],
-    "retr_argmax_rows_ws": [_I, _P, _L, _I, _I, _P, _P, _P],
-    "retr_dropout_apply": [_I, _P, _L, _P, _L, _I, _I, _F, _U64, _P],
-    "retr_cast": [_I, _P, _P, _L, _P],
-    "retr_add_pos_fwd": [_I, _P, _L, _I, _I, _P, _I, _P, _P, _L, _P],
-    "retr_sum2": [_I, _P, _P, _L, _P, _P],
-    "retr_pos_grad": [_I, _P, _L, _I, _I, _I, _P, _P],
-    "retr_pos_grad_set": [_I, _P, _L, _I, _I, _I, _P, _P],
-    "retr_pos_grad_multi": [_I, _I, ctypes.POINTER(PosItem), _I, _I, _P, _I, _P],
-    "retr_dec_gemm": [_P, _P, _I, _I, _P, _P, _I, _P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _P],
-    "retr_dec_rows": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P],
-    "retr_dec_embed_rows": [_P, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P, _F, _P, _P, _P],
-    "retr_greedy_select": [_I, _P, _L, _I, _I, _P, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, _P,
-                           _P],
-    "retr_greedy_select2": [_I, _P, _L, _I, _I, _P, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, _P,
-                            _I, _P],
-    "retr_dec_attn_row": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F,
-                          _P, _P, _P, _P, _P],
-    "retr_dec_ffn": [_P, _I, _I, _P, _P, _P, _I, _P, _P],
-    "retr_dec_ffn_ln": [_P, _P, _I, _P, _P, _P, _F, _P, _I, _I, _P, _P, _P, _I, _P, _P],
-    "retr_dec_linear_bf16": [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _P],
-    "retr_dec_linear_f32": [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _P, _L, _P],
-    "retr_dec_linear3_f32": [_I, _P, _L, _P, _L, _P, _P, _L, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _L, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _L, _I, _I, _P, _L, _I, _I, _P],
-    "retr_dec_self_f32": [_I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P,
-                          _P, _P, _F, _P, _P, _F, _P, _P, _P],
-    "retr_dec_cross_f32": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _P,
-                           _P, _P, _P],
-    "retr_dec_ffn_f32": [_P, _P, _I, _P, _P, _P, _F, _P, _I, _I, _P, _P, _P, _I, _P, _P],
-    "retr_dec_rows_f32": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _F, _P, _P],
-    "retr_dec_ffn_ln64": [_P, _P, _I, _P, _P, _P, _F, _P, _I, _I, _P, _P, _P, _I, _P, _P],
-    "retr_dec_ffn_ln128": [_P, _P, _I, _P, _P, _P, _F, _P, _I, _I, _P, _P, _P, _I, _P, _P],
-    "retr_dec_self_heads_ln": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I,
-                               _P, _P, _P, _F, _P, _P, _P],
-    "retr_dec_self_heads": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
-    "retr_dec_cross_heads": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I,
-                             _P, _P, _P, _P],
-    "retr_dec_self_heads_embed": [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P,
-                                  _P, _P, _P, _P, _F, _P, _P, _P],
-    "retr_dec_self_heads_mr": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I,
-                               _P, _P, _P, _F, _P, _P, _I, _P],
-    "retr_dec_cross_heads_mr": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _I,
-                                _P, _P, _P, _I, _P],
-    "retr_adamw_sumsq": [_P, _L, _P, _I, _P, _P],
-    "retr_adamw_update": [_P, _P, _P, _P, _L, _P, _D, _D, _F, _P, _F, _P, _I, _F, _P, _P],
-    "retr_adamw_update2": [_P, _P, _P, _P, _L, _P, _D, _D, _F, _P, _F, _P, _I, _F, _P, _I, _P],
-}
-_RESTYPE = {"retr_last_error": ctypes.c_char_p, "retr_attention_bwd_workspace": _SZ,
-            "retr_attention_dropout_mask_bytes": _SZ,
-            "retr_layernorm_bwd_workspace": _SZ, "retr_embed_ln_bwd_workspace": _SZ,
-            "retr_linear_wgrad_group_workspace": _SZ, "retr_linear_wgrad_batch_table_bytes": _SZ, "retr_conv2d_wgrad_group_table_bytes": _SZ, "retr_conv_wgrad_unpack_group_table_bytes": _SZ, "retr_argmax_workspace": _SZ,
-            "retr_set_deterministic": None,
-            "retr_set_seed_base": None}
+LinearFwdDesc = STRUCTS["retr_linear_fwd_desc"]
+LinearDgradDesc = STRUCTS["retr_linear_dgrad_desc"]
+LinearWgradDesc = STRUCTS["retr_linear_wgrad_desc"]
+ConvWgradDesc = STRUCTS["retr_conv_wgrad_desc"]
+ConvUnpackDesc = STRUCTS["retr_conv_unpack_desc"]
+PosItem = STRUCTS["retr_pos_item"]
+LnOut = STRUCTS["retr_ln_out"]
+ConvPackDesc = STRUCTS["retr_conv_pack_desc"]
+CatRowsDesc = STRUCTS["retr_cat_rows_desc"]
+SlabSumDesc = STRUCTS["retr_slab_sum_desc"]
+PipeItem = STRUCTS["retr_pipe_item"]
 
 _lib = None
 
@@ -264,10 +153,10 @@ def load():
                 f"retr_amd: native library {LIB_PATH} is missing; build it with `make` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, args in _SIGS.items():
+        for name, (restype, params) in FUNCTIONS.items():
             fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = _RESTYPE.get(name, ctypes.c_int)
+            fn.argtypes = [t for _, t in params]
+            fn.restype = restype
         # RETR_TUNE_<knob>=<value> in the environment presets a tuning knob (A/B runs)
         # (a malformed value or an unknown knob number is reported and skipped: it must not
         # break every import of the package)
@@ -287,7 +176,28 @@ def load():
 
 
 def exported_symbols():
-    return list(_SIGS)
+    return list(FUNCTIONS)
+
+
+def tune(name, value):
+    """Set the tuning knob RETR_TUNE_<name>; returns its previous value."""
+    if name not in TUNE:
+        raise KeyError(f"no tuning knob {name!r}; the knobs are {', '.join(TUNE)}")
+    return load().retr_tune(TUNE[name], value)
+
+
+@contextlib.contextmanager
+def tuned(**knobs):
+    """``with tuned(ATTN_MODE=2, ATTN_SPLIT=1):`` sets the knobs for the block and puts back
+    the values they had before, in reverse order, however the block ends."""
+    previous = []
+    try:
+        for name, value in knobs.items():
+            previous.append((name, tune(name, value)))
+        yield
+    finally:
+        for name, value in reversed(previous):
+            tune(name, value)
 
 
 _probe = None

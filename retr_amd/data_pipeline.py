@@ -113,17 +113,6 @@ def jitter_params(generator=None):
     return [(i + 1, fs[i]) for i in perm if i != 3]
 
 
-class _Item(ctypes.Structure):
-    _fields_ = [("src_off", ctypes.c_longlong), ("tmp_off", ctypes.c_longlong),
-                ("H", ctypes.c_int), ("W", ctypes.c_int), ("x0", ctypes.c_int),
-                ("y0", ctypes.c_int), ("rw", ctypes.c_int), ("rh", ctypes.c_int),
-                ("bx", ctypes.c_int), ("by", ctypes.c_int), ("bw", ctypes.c_int),
-                ("bh", ctypes.c_int), ("D", ctypes.c_int), ("ox", ctypes.c_int),
-                ("oy", ctypes.c_int), ("mx", ctypes.c_int), ("my", ctypes.c_int),
-                ("coef_off", ctypes.c_int), ("ksize", ctypes.c_int), ("win_off", ctypes.c_int),
-                ("ops", ctypes.c_int), ("f", ctypes.c_float * 3), ("pad_", ctypes.c_int * 2)]
-
-
 def encode(images, bbs, size, jitters=None, context=False, device=None, want_u8=False):
     """Run the pipeline on a batch.  images: HxWx3 uint8 arrays; bbs: (x, y, w, h);
     jitters: per item None or [(op, factor)].  Returns (fp32 [B, 3, S, S], bool [B, S, S]) and,
@@ -131,7 +120,7 @@ def encode(images, bbs, size, jitters=None, context=False, device=None, want_u8=
     dev = torch.device(device) if device is not None else torch.device("cuda")
     _lib.require_device(torch.empty(0, device=dev))
     n, S = len(images), int(size)
-    items = (_Item * max(n, 1))()
+    items = (_lib.PipeItem * max(n, 1))()
     coef_parts, win_parts, src_parts = [], [], []
     coef_len = win_len = src_len = tmp_len = 0
     max_d = 1
@@ -185,14 +174,14 @@ def encode(images, bbs, size, jitters=None, context=False, device=None, want_u8=
     src = torch.from_numpy(np.concatenate(src_parts)).pin_memory().to(dev, non_blocking=True)
     coef = torch.from_numpy(np.concatenate(coef_parts).astype(np.int32)).to(dev)
     win = torch.from_numpy(np.concatenate(win_parts).astype(np.int32)).to(dev)
-    desc = torch.frombuffer(bytearray(bytes(items)[: n * ctypes.sizeof(_Item)]),
+    desc = torch.frombuffer(bytearray(bytes(items)[: n * ctypes.sizeof(_lib.PipeItem)]),
                             dtype=torch.uint8).to(dev)
     tmp = torch.empty(tmp_len, dtype=torch.uint8, device=dev)
     mean = (ctypes.c_float * 3)(*IMAGENET_MEAN)
     std = (ctypes.c_float * 3)(*IMAGENET_STD)
-    call("retr_pipe_run", ptr(src), ptr(desc), n, ptr(coef), ptr(win), ptr(tmp), max_d, ptr(u8),
-         ptr(out), ptr(mask), S, ctypes.cast(mean, ctypes.c_void_p),
-         ctypes.cast(std, ctypes.c_void_p), _st())
+    call("retr_pipe_run", ptr(src), ctypes.cast(ptr(desc), ctypes.POINTER(_lib.PipeItem)), n,
+         ptr(coef), ptr(win), ptr(tmp), max_d, ptr(u8), ptr(out), ptr(mask), S,
+         ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), _st())
     # the host buffers above must outlive the copies; the stream orders everything after them
     torch.cuda.current_stream(dev).synchronize()
     return (out, mask, u8) if want_u8 else (out, mask)

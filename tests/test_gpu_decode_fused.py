@@ -516,37 +516,37 @@ def test_dec_heads_multi_row_matches_per_row(rb, kv_group, prologue):
     beta = torch.randn(C, generator=g).to(DEV) * 0.1
     qpos = torch.randn(C, generator=g).to(DEV)
     outs = []
-    _lib.load().retr_tune(31, 1)          # the per-row kernels' two-wave layout (the mr layout)
-    for r_b in (1, rb):
-        kc1, vc1 = kc.clone(), vc.clone()
-        slab = torch.full((H, R, C), float("nan"), device=DEV)
-        xout = torch.full((R, C), float("nan"), device=DEV)
-        if prologue:
-            call("retr_dec_self_heads_mr", None, None, R, C, H, ptr(win), ptr(bin_), ptr(kc1),
-                 ptr(vc1), i, T, ptr(anc), ptr(wo), ptr(slab), ptr(xin), ptr(slabs), nsl, ptr(b2),
-                 ptr(gamma), ptr(beta), 1e-5, ptr(qpos), ptr(xout), r_b, ops._st())
-        else:
-            call("retr_dec_self_heads_mr", ptr(n), ptr(npos), R, C, H, ptr(win), ptr(bin_),
-                 ptr(kc1), ptr(vc1), i, T, ptr(anc), ptr(wo), ptr(slab), None, None, 0, None,
-                 None, None, 0.0, None, None, r_b, ops._st())
-        B = R // kv_group
-        km = bf(torch.randn(B * S, C, generator=_g(7)))
-        vm = bf(torch.randn(B * S, C, generator=_g(8)))
-        kpm = torch.zeros(B, S, dtype=torch.uint8)
-        kpm[B - 1, -13:] = 1
-        kpm = kpm.to(DEV)
-        x = torch.randn(R, C, generator=_g(9)).to(DEV)
-        wq = bf(torch.randn(3 * C, C, generator=_g(10)) / math.sqrt(C))
-        bq = torch.randn(3 * C, generator=_g(11)).to(DEV) * 0.1
-        wo2 = bf(torch.randn(C, C, generator=_g(12)) / math.sqrt(C))
-        xo = torch.full((R, C), float("nan"), device=DEV)
-        slab2 = torch.full((H, R, C), float("nan"), device=DEV)
-        call("retr_dec_cross_heads_mr", ptr(slab), ptr(x), ptr(b2), ptr(xo), R, C, H, ptr(gamma),
-             ptr(beta), 1e-5, ptr(qpos), ptr(wq), ptr(bq), ptr(km), ptr(vm), S, kv_group,
-             ptr(kpm), ptr(wo2), ptr(slab2), r_b, ops._st())
-        torch.cuda.synchronize()
-        outs.append((slab, kc1, vc1, xo, slab2) + ((xout,) if prologue else ()))
-    _lib.load().retr_tune(31, 0)
+    with _lib.tuned(DEC_WAVES=1):         # the per-row kernels' two-wave layout (the mr layout)
+        for r_b in (1, rb):
+            kc1, vc1 = kc.clone(), vc.clone()
+            slab = torch.full((H, R, C), float("nan"), device=DEV)
+            xout = torch.full((R, C), float("nan"), device=DEV)
+            if prologue:
+                call("retr_dec_self_heads_mr", None, None, R, C, H, ptr(win), ptr(bin_),
+                     ptr(kc1), ptr(vc1), i, T, ptr(anc), ptr(wo), ptr(slab), ptr(xin),
+                     ptr(slabs), nsl, ptr(b2), ptr(gamma), ptr(beta), 1e-5, ptr(qpos),
+                     ptr(xout), r_b, ops._st())
+            else:
+                call("retr_dec_self_heads_mr", ptr(n), ptr(npos), R, C, H, ptr(win), ptr(bin_),
+                     ptr(kc1), ptr(vc1), i, T, ptr(anc), ptr(wo), ptr(slab), None, None, 0,
+                     None, None, None, 0.0, None, None, r_b, ops._st())
+            B = R // kv_group
+            km = bf(torch.randn(B * S, C, generator=_g(7)))
+            vm = bf(torch.randn(B * S, C, generator=_g(8)))
+            kpm = torch.zeros(B, S, dtype=torch.uint8)
+            kpm[B - 1, -13:] = 1
+            kpm = kpm.to(DEV)
+            x = torch.randn(R, C, generator=_g(9)).to(DEV)
+            wq = bf(torch.randn(3 * C, C, generator=_g(10)) / math.sqrt(C))
+            bq = torch.randn(3 * C, generator=_g(11)).to(DEV) * 0.1
+            wo2 = bf(torch.randn(C, C, generator=_g(12)) / math.sqrt(C))
+            xo = torch.full((R, C), float("nan"), device=DEV)
+            slab2 = torch.full((H, R, C), float("nan"), device=DEV)
+            call("retr_dec_cross_heads_mr", ptr(slab), ptr(x), ptr(b2), ptr(xo), R, C, H,
+                 ptr(gamma), ptr(beta), 1e-5, ptr(qpos), ptr(wq), ptr(bq), ptr(km), ptr(vm), S,
+                 kv_group, ptr(kpm), ptr(wo2), ptr(slab2), r_b, ops._st())
+            torch.cuda.synchronize()
+            outs.append((slab, kc1, vc1, xo, slab2) + ((xout,) if prologue else ()))
     for a, b in zip(*outs):
         assert torch.equal(a, b)
     assert not torch.isnan(outs[1][-1]).any()
@@ -570,18 +570,17 @@ def test_dec_multi_row_beam_step_matches():
         for rb in (None, 1):
             # (the embedding fold runs on per-row blocks only: off for both, same arithmetic)
             dec.DEC_ROWS_PER_BLOCK, dec.DEC_EMBED_FOLD = rb, False
-            _lib.load().retr_tune(31, 1)    # two-wave per-row kernels: the mr kernels' arithmetic
-            model._retr_decode_states = {}
-            bm = dec.IncrementalBeam(model, 5)
-            ids = bm(s, T, 101, 102)
-            res.append(ids)
-            if rb is None:
-                assert dec._rows_per_block(B * 5, 256, 8, 5, 1, 197) == (5, 5)
-                ids_e = dec.IncrementalBeam(model, 5, use_graphs=False)(s, T, 101, 102)
-                assert torch.equal(ids, ids_e)
+            with _lib.tuned(DEC_WAVES=1):   # two-wave per-row kernels: the mr kernels' arithmetic
+                model._retr_decode_states = {}
+                bm = dec.IncrementalBeam(model, 5)
+                ids = bm(s, T, 101, 102)
+                res.append(ids)
+                if rb is None:
+                    assert dec._rows_per_block(B * 5, 256, 8, 5, 1, 197) == (5, 5)
+                    ids_e = dec.IncrementalBeam(model, 5, use_graphs=False)(s, T, 101, 102)
+                    assert torch.equal(ids, ids_e)
     finally:
         dec.DEC_ROWS_PER_BLOCK, dec.DEC_EMBED_FOLD = old
-        _lib.load().retr_tune(31, 0)
         model._retr_decode_states = {}
     assert torch.equal(res[0], res[1])
 

@@ -260,15 +260,12 @@ def test_conv_wgrad_b32_loader_bitwise(cfg):
     lib = _lib.load()
     splits = lib.retr_conv2d_wgrad_splits(ops.dcode(bf), N, H, H, cp, Co, k, k, s, p, d)
     out = []
-    try:
-        for knob in (0, 1):
-            lib.retr_tune(16, knob)
+    for knob in (0, 1):
+        with _lib.tuned(WGRAD_B32=knob):
             ws = torch.full((splits, Co, k * k * cp), float("nan"), device=DEV)
             call("retr_conv2d_wgrad", ops.dcode(bf), ptr(gn), ptr(xn), N, H, H, cp, ptr(ws), Co,
                  k, k, s, p, d, ops._st())
             out.append(ws)
-    finally:
-        lib.retr_tune(16, 0)
     assert not torch.isnan(out[0]).any()
     assert torch.equal(out[0], out[1])
 
@@ -633,9 +630,7 @@ def test_attention_resident_equals_streaming(B, H, Lq, Lk, hd, causal, masked, p
         kpm = kpm.to(DEV)
     outs = []
     for mode, split in ((1, 1), (2, 1), (0, 0)):
-        _lib.load().retr_tune(5, mode)
-        _lib.load().retr_tune(10, split)
-        try:
+        with _lib.tuned(ATTN_MODE=mode, ATTN_SPLIT=split):
             o = torch.empty(B * Lq, C, dtype=bf, device=DEV)
             lse = torch.empty(B * H * Lq, device=DEV)
             ops.k_attention_fwd(q, k, v, o, B, H, Lq, Lk, hd, kpm, causal, p, 1234, lse)
@@ -644,9 +639,6 @@ def test_attention_resident_equals_streaming(B, H, Lq, Lk, hd, causal, masked, p
                                 1234)
             torch.cuda.synchronize()
             outs.append((o, lse, dq, dk, dv))
-        finally:
-            _lib.load().retr_tune(5, 0)
-            _lib.load().retr_tune(2, 0)
     for a, b in zip(outs[0], outs[1]):
         assert torch.equal(a, b)
     # the default split backward (two waves per 32 rows, even + odd tile partials added at the
@@ -995,8 +987,7 @@ def test_attention_saved_dropout_bits_equal_rehash(B, H, Lq, Lk, hd, causal, mas
         kpm[:, Lk - Lk // 5:] = 1
         kpm = kpm.to(DEV)
     outs = []
-    _lib.load().retr_tune(5, mode)
-    try:
+    with _lib.tuned(ATTN_MODE=mode):
         for use in (False, True):
             dm = ops.attn_dmask(B, H, Lq, Lk, p, bf, hd, DEV) if use else None
             if dm is not None:
@@ -1009,8 +1000,6 @@ def test_attention_saved_dropout_bits_equal_rehash(B, H, Lq, Lk, hd, causal, mas
                                 99, dm)
             torch.cuda.synchronize()
             outs.append((o, lse, dq, dk, dv))
-    finally:
-        _lib.load().retr_tune(5, 0)
     for a, b in zip(*outs):
         assert torch.equal(a, b)
     if causal:   # words of key tiles past a block's diagonal are never written
@@ -1047,10 +1036,8 @@ def test_attention_pregenerated_keep_bits(B, H, Lq, Lk, hd, causal, masked, fs):
         kpm[:, Lk - Lk // 5:] = 1
         kpm = kpm.to(DEV)
     outs = {}
-    _lib.load().retr_tune(12, fs)
-    try:
-        for pre in (0, 1):
-            _lib.load().retr_tune(26, pre)
+    for pre in (0, 1):
+        with _lib.tuned(ATTN_FSPLIT=fs, ATTN_KEEPPRE=pre):
             dm = ops.attn_dmask(B, H, Lq, Lk, p, bf, hd, DEV)
             dm.fill_(0)
             o = torch.empty(B * Lq, C, dtype=bf, device=DEV)
@@ -1058,9 +1045,6 @@ def test_attention_pregenerated_keep_bits(B, H, Lq, Lk, hd, causal, masked, fs):
             ops.k_attention_fwd(q, k, v, o, B, H, Lq, Lk, hd, kpm, causal, p, 11, lse, None, dm)
             torch.cuda.synchronize()
             outs[pre] = (o, lse, dm)
-    finally:
-        _lib.load().retr_tune(26, 0)
-        _lib.load().retr_tune(12, 0)
     (o1, l1, d1), (o0, l0, d0) = outs[1], outs[0]     # pregenerated, hashing forward
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
     w = d0 != 0 if causal else torch.ones_like(d0, dtype=torch.bool)
@@ -1087,9 +1071,8 @@ def test_attention_forward_key_split(B, H, Lq, Lk, hd, causal, masked):
         kpm[:, Lk - Lk // 5:] = 1
         kpm = kpm.to(DEV)
     outs = {}
-    try:
-        for fs in (1, 2, 3, 4):
-            _lib.load().retr_tune(12, fs)
+    for fs in (1, 2, 3, 4):
+        with _lib.tuned(ATTN_FSPLIT=fs):
             runs = []
             for _ in range(2):
                 dm = ops.attn_dmask(B, H, Lq, Lk, p, bf, hd, DEV)
@@ -1102,8 +1085,6 @@ def test_attention_forward_key_split(B, H, Lq, Lk, hd, causal, masked):
             for a, b in zip(*runs):
                 assert torch.equal(a, b), fs
             outs[fs] = runs[0]
-    finally:
-        _lib.load().retr_tune(12, 0)
     o1, l1, d1 = outs[1]
     for fs in (2, 3, 4):
         o, lse, dm = outs[fs]
@@ -1129,8 +1110,7 @@ def test_shortk_single_stage_tiles_bitwise(kind):
     bf = torch.bfloat16
     outs, ref = [], None
     for off in (1, 0):
-        _lib.load().retr_tune(14, off)
-        try:
+        with _lib.tuned(SHORTK=off):
             if kind.startswith("fwd1x1"):   # 80x80x128 -> 512 + residual + ReLU (layer2 conv3)
                 # or 20x20x512 -> 2048 (layer4 conv3, <= 8192 pixels)
                 Nb, H, C, Co = (2, 80, 128, 512) if kind == "fwd1x1" else (4, 20, 512, 2048)
@@ -1181,8 +1161,6 @@ def test_shortk_single_stage_tiles_bitwise(kind):
                      None, 0, 0.0, 0, ops._st())
             torch.cuda.synchronize()
             outs.append(y)
-        finally:
-            _lib.load().retr_tune(14, 0)
     assert torch.equal(outs[0], outs[1])
     assert rel_err(outs[1].float(), ref) < 1e-2
 
@@ -1265,9 +1243,8 @@ def test_wgrad_group_last_arriver_equals_slab_sum(case):
     nparts, C = 37, 256
     parts = torch.randn(nparts * 2 * C, generator=g).to(DEV)
     outs = []
-    try:
-        for knob in (0, 1, 1, 1):
-            _lib.load().retr_tune(17, knob)
+    for knob in (0, 1, 1, 1):
+        with _lib.tuned(WGRAD_FUSED=knob):
             for acc in (False, True):
                 run = []
                 for dy, x, M, N, K, has_b in items:
@@ -1283,8 +1260,6 @@ def test_wgrad_group_last_arriver_equals_slab_sum(case):
                 torch.cuda.synchronize()
                 outs.append([t.clone() for it in run for t in it[2:4] if t is not None] +
                             [gam.clone(), bet.clone()])
-    finally:
-        _lib.load().retr_tune(17, 0)
     n = 2
     for k in range(1, 4):
         for a in range(n):
@@ -1389,8 +1364,7 @@ def test_wgrad_batch_matches_fp32_and_is_batching_invariant(tile):
         return [t.clone() for it in run for t in it[2:4] if t is not None] + \
                [e[4].clone() for e in extra]
 
-    try:
-        _lib.load().retr_tune(2, tile)          # RETR_TUNE_WGRAD_TILE
+    with _lib.tuned(WGRAD_TILE=tile):
         res = {}
         for acc in (False, True):
             run, extra = fresh(acc)
@@ -1422,8 +1396,6 @@ def test_wgrad_batch_matches_fp32_and_is_batching_invariant(tile):
         torch.cuda.synchronize()
         for a, b in zip(res[True], outs(run, extra)):
             assert torch.equal(a, b)
-    finally:
-        _lib.load().retr_tune(2, 0)
 
 
 def test_conv_wgrad_group_matches_fp32_and_single_path():
@@ -1505,11 +1477,8 @@ def test_conv_wgrad_group_matches_fp32_and_single_path():
     for knob in (-1, 37):
         for o in outs:
             o.fill_(float("nan"))
-        try:
-            _lib.load().retr_tune(28, knob)
+        with _lib.tuned(UNPACK_GRID=knob):
             call("retr_conv_wgrad_unpack_group", n, ua, ptr(utab), utab.numel(), ops._st())
-        finally:
-            _lib.load().retr_tune(28, 0)
         for a, b in zip(first, outs):
             assert torch.equal(a, b), knob
     # accumulate mode: grad += scale * sum (the row kernel's staged and 16-byte paths)
@@ -1541,17 +1510,14 @@ def test_splitk_fused_equals_slab_epilogue(M, N, K):
     gate = torch.randn(M, N, generator=g).to(DEV).to(bf)
     wt = ops._TView(w.t().contiguous())
     outs = []
-    try:
-        for knob in (0, 1, 1, 1):
-            _lib.load().retr_tune(18, knob)
+    for knob in (0, 1, 1, 1):
+        with _lib.tuned(SPLITK_FUSED=knob):
             y = torch.full((M, N), float("nan"), device=DEV)
             ops.k_linear_fwd(x, w, b, y, res=res, drop_p=0.1, seed=91)
             dx = torch.full((M, N), float("nan"), dtype=bf, device=DEV)
             ops.k_linear_dgrad(dy, wt, dx, addend=add, gate=gate)
             torch.cuda.synchronize()
             outs.append((y, dx))
-    finally:
-        _lib.load().retr_tune(18, 0)
     for y, dx in outs[1:]:
         assert torch.equal(y, outs[0][0])
         assert torch.equal(dx, outs[0][1])
@@ -1579,9 +1545,8 @@ def test_conv3x3_direct_matches_implicit_gemm_and_fp32(nb, H, W, C, Co):
     dy = torch.randn(nb, H, W, Co, generator=g).to(DEV, bf)
     gate = torch.randn(nb, H, W, C, generator=g).to(DEV, bf)
     res = {}
-    try:
-        for knob in (2, 1):                     # 2: the direct kernel on every map (>= 16 wide)
-            _lib.load().retr_tune(21, knob)
+    for knob in (2, 1):                         # 2: the direct kernel on every map (>= 16 wide)
+        with _lib.tuned(CONV3X3=knob):
             y = torch.full((nb, H, W, Co), float("nan"), dtype=bf, device=DEV)
             call("retr_conv2d_fwd", 1, ptr(x), nb, H, W, C, ptr(wf), ptr(b), None, ptr(y), Co,
                  3, 3, 1, 1, 1, 1, ops._st())
@@ -1590,8 +1555,6 @@ def test_conv3x3_direct_matches_implicit_gemm_and_fp32(nb, H, W, C, Co):
                  1, None, ptr(gate), ops._st())
             torch.cuda.synchronize()
             res[knob] = (y.float(), dx.float())
-    finally:
-        _lib.load().retr_tune(21, 0)
     xr = x.float().permute(0, 3, 1, 2)
     wr = wf.float().permute(0, 3, 1, 2)
     yref = torch.relu(F.conv2d(xr, wr, b, padding=1)).permute(0, 2, 3, 1)
@@ -1630,20 +1593,15 @@ def test_conv3x3_direct_every_tile_variant():
         torch.cuda.synchronize()
         return y.float(), dx.float()
 
-    lib = _lib.load()
-    try:
-        lib.retr_tune(21, 1)                    # the implicit GEMM
+    with _lib.tuned(CONV3X3=1):                 # the implicit GEMM
         ref = run()
-        lib.retr_tune(21, 2)                    # the direct kernel on every map >= 16 wide
+    with _lib.tuned(CONV3X3=2):                 # the direct kernel on every map >= 16 wide
         for v in range(1, 14):
-            lib.retr_tune(22, v)
-            a, a2 = run(), run()
-            for got, again, want in zip(a, a2, ref):
-                assert torch.equal(got, again), v
-                assert rel_err(got, want) < 5e-3, (v, rel_err(got, want))
-    finally:
-        lib.retr_tune(21, 0)
-        lib.retr_tune(22, 0)
+            with _lib.tuned(C3_TILE=v):
+                a, a2 = run(), run()
+                for got, again, want in zip(a, a2, ref):
+                    assert torch.equal(got, again), v
+                    assert rel_err(got, want) < 5e-3, (v, rel_err(got, want))
 
 
 @pytest.mark.parametrize("M,N,K", [(6400, 2048, 256), (2048, 2048, 256), (1000, 1800, 192),
@@ -1662,9 +1620,8 @@ def test_panel_gemm_equals_tile_gemm(M, N, K):
     w2 = (torch.randn(K, N, generator=g) / math.sqrt(K)).to(DEV).to(bf)
     gate = torch.randn(M, N, generator=g).to(DEV).to(bf)
     outs = {}
-    try:
-        for knob in (0, 1):
-            _lib.load().retr_tune(23, knob)
+    for knob in (0, 1):
+        with _lib.tuned(PANEL=knob):
             y = torch.full((M, N), float("nan"), dtype=bf, device=DEV)
             ops.k_linear_fwd(x, w, b, y, relu=1)
             d1 = torch.full((M, N), float("nan"), dtype=bf, device=DEV)
@@ -1673,8 +1630,6 @@ def test_panel_gemm_equals_tile_gemm(M, N, K):
             ops.k_linear_dgrad(dy, ops._TView(w2), d2, gate=gate)            # W [K][N] transposed
             torch.cuda.synchronize()
             outs[knob] = (y, d1, d2)
-    finally:
-        _lib.load().retr_tune(23, 0)
     for a, c in zip(outs[1], outs[0]):
         assert torch.equal(a, c)
     ref = torch.relu(x.float() @ w.float().t() + b)
@@ -1775,12 +1730,11 @@ def test_linear_k256_all_steps_at_once_equals_loop(M, N, kind):
     """K = 256 linears on few output tiles: gemm_short_kernel (every K-step fetched at once,
     RETR_TUNE_LIN_K256 = 0 / 2) gives the bits of gemm_kernel's double-buffered loop (1), and
     both match an fp32 reference (ragged M / N included)."""
-    bf, K, lib = torch.bfloat16, 256, _lib.load()
+    bf, K = torch.bfloat16, 256
     g = torch.Generator(device=DEV).manual_seed(M + N)
     outs = []
-    try:
-        for knob in (1, 0):
-            lib.retr_tune(33, knob)
+    for knob in (1, 0):
+        with _lib.tuned(LIN_K256=knob):
             if kind.startswith("fwd"):
                 x = torch.randn(M, K, device=DEV, generator=g).to(bf) if not outs else x
                 w = (torch.randn(N, K, device=DEV, generator=g) * 0.05).to(bf) if not outs else w
@@ -1810,8 +1764,6 @@ def test_linear_k256_all_steps_at_once_equals_loop(M, N, kind):
                 ref = (dy.float() @ wt.float() + add.float()) * (gate.float() > 0)
             torch.cuda.synchronize()
             outs.append(y.clone())
-    finally:
-        lib.retr_tune(33, 0)
     assert torch.equal(outs[0], outs[1])
     err = (outs[1].float() - ref).abs().max().item()
     assert err < 0.05 * max(1.0, ref.abs().max().item()), err

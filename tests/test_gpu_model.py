@@ -674,18 +674,15 @@ def test_grouped_conv_wgrad_tile_layouts_bitwise():
     caps, cap_mask = synthetic_captions(2, 16, 1000, seed=4)
     s = NestedTensor(images.to(DEV), mask.to(DEV))
     res = []
-    try:
-        resnet.CONV_WGRAD_GROUP = True
-        for layout in (0, 1, 2, 3):
-            _lib.load().retr_tune(29, layout)
+    resnet.CONV_WGRAD_GROUP = True
+    for layout in (0, 1, 2, 3):
+        with _lib.tuned(CW_WAVES=layout):
             model.zero_grad(set_to_none=True)
             out = model(s, caps[:, :-1].to(DEV), cap_mask[:, :-1].to(DEV))
             crit(out.permute(0, 2, 1), caps[:, 1:].to(DEV)).backward()
             torch.cuda.synchronize()
             res.append({n: p.grad.detach().clone() for n, p in model.named_parameters()
                         if p.grad is not None and n.startswith("backbone")})
-    finally:
-        _lib.load().retr_tune(29, 0)
     assert len(res[0]) > 20
     for r in res[1:]:
         for n in res[0]:

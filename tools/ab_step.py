@@ -15,7 +15,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from retr_amd import ops, resnet  # noqa: E402
-from retr_amd._lib import load  # noqa: E402
+from retr_amd._lib import tune  # noqa: E402
 from retr_amd.engine import GraphedTrainStep  # noqa: E402
 from retr_amd.models.utils import NestedTensor  # noqa: E402
 from retr_amd.synthetic import synthetic_captions, synthetic_images  # noqa: E402
@@ -28,73 +28,73 @@ VARIANTS = {
     "nofuse_ln": {("ATTR", "FUSE_LN_BWD"): False},
     "no_lnparams": {("ATTR", "FUSE_LN_PARAMS"): False},
     "no_dmask": {("ATTR", "ATTN_DMASK"): False},
-    "split_off": {("TUNE", 10): 1},
-    "split_all": {("TUNE", 10): 2},
-    "split_dq_all": {("TUNE", 10): 2},
-    "no_dmask_split_off": {("ATTR", "ATTN_DMASK"): False, ("TUNE", 10): 1},
+    "split_off": {("TUNE", "ATTN_SPLIT"): 1},
+    "split_all": {("TUNE", "ATTN_SPLIT"): 2},
+    "split_dq_all": {("TUNE", "ATTN_SPLIT"): 2},
+    "no_dmask_split_off": {("ATTR", "ATTN_DMASK"): False, ("TUNE", "ATTN_SPLIT"): 1},
     "no_stem_pool": {("ENV", "RETR_STEM_POOL"): "0"},
-    "lin_small": {("TUNE", 13): 2},
-    "fsplit_off": {("TUNE", 12): 1},
-    "shortk_off": {("TUNE", 14): 1},
-    "grp_s1": {("TUNE", 1): 1},
-    "wgrp_s1": {("TUNE", 3): 1},
-    "cwg_s1": {("TUNE", 9): 3},
-    "adamw_nt": {("TUNE", 15): 1},
-    "adamw_plain": {("TUNE", 15): 2},
-    "adamw_u2": {("TUNE", 15): 3},
-    "lin_k256": {("TUNE", 33): 2},
-    "lin_k256_loop": {("TUNE", 33): 1},
-    "gemm_nt": {("TUNE", 7): 1},
+    "lin_small": {("TUNE", "LIN_SMALL"): 2},
+    "fsplit_off": {("TUNE", "ATTN_FSPLIT"): 1},
+    "shortk_off": {("TUNE", "SHORTK"): 1},
+    "grp_s1": {("TUNE", "GROUP_STAGES"): 1},
+    "wgrp_s1": {("TUNE", "WGRAD_STAGES"): 1},
+    "cwg_s1": {("TUNE", "CONV_WGRAD_TILE"): 3},
+    "adamw_nt": {("TUNE", "ADAMW_NT"): 1},
+    "adamw_plain": {("TUNE", "ADAMW_NT"): 2},
+    "adamw_u2": {("TUNE", "ADAMW_NT"): 3},
+    "lin_k256": {("TUNE", "LIN_K256"): 2},
+    "lin_k256_loop": {("TUNE", "LIN_K256"): 1},
+    "gemm_nt": {("TUNE", "NT_STORE"): 1},
     "ce_unfused": {("ATTR", "FUSED_CE"): False},
-    "wgrad_b64": {("TUNE", 16): 1},
-    "grp_s4": {("TUNE", 1): 4},
-    "wgrp_s4": {("TUNE", 3): 4},
-    "wkc256": {("TUNE", 4): 256},
-    "wkc1024": {("TUNE", 4): 1024},
-    "wtile128": {("TUNE", 2): 128},
-    "wthr50k": {("TUNE", 2): 50000},
-    "wthr100k": {("TUNE", 2): 100000},
-    "wthr120k": {("TUNE", 2): 120000},
-    "wthr400k": {("TUNE", 2): 400000},
-    "wgrad_fused": {("TUNE", 17): 1},
+    "wgrad_b64": {("TUNE", "WGRAD_B32"): 1},
+    "grp_s4": {("TUNE", "GROUP_STAGES"): 4},
+    "wgrp_s4": {("TUNE", "WGRAD_STAGES"): 4},
+    "wkc256": {("TUNE", "WGRAD_KC"): 256},
+    "wkc1024": {("TUNE", "WGRAD_KC"): 1024},
+    "wtile128": {("TUNE", "WGRAD_TILE"): 128},
+    "wthr50k": {("TUNE", "WGRAD_TILE"): 50000},
+    "wthr100k": {("TUNE", "WGRAD_TILE"): 100000},
+    "wthr120k": {("TUNE", "WGRAD_TILE"): 120000},
+    "wthr400k": {("TUNE", "WGRAD_TILE"): 400000},
+    "wgrad_fused": {("TUNE", "WGRAD_FUSED"): 1},
     "ffn_fused": {("ATTR", "FUSE_FFN"): True},
-    "wkc2048": {("TUNE", 4): 2048},
-    "wkc3200": {("TUNE", 4): 3200},
+    "wkc2048": {("TUNE", "WGRAD_KC"): 2048},
+    "wkc3200": {("TUNE", "WGRAD_KC"): 3200},
     "wdefer_off": {("ATTR", "WGRAD_DEFER"): False},
-    "wb64": {("TUNE", 2): 64},
-    "wb128": {("TUNE", 2): 128},
+    "wb64": {("TUNE", "WGRAD_TILE"): 64},
+    "wb128": {("TUNE", "WGRAD_TILE"): 128},
     "wside_on": {("ATTR", "WGRAD_SIDE"): True},
     "cwg_off": {("RESNET", "CONV_WGRAD_GROUP"): False},
-    "skf": {("TUNE", 18): 1},
-    "wbc16": {("TUNE", 19): 16},
-    "wbc64": {("TUNE", 19): 64},
-    "cwc16": {("TUNE", 20): 16},
-    "cwc64": {("TUNE", 20): 64},
-    "c16": {("TUNE", 19): 16, ("TUNE", 20): 16},
-    "c3_off": {("TUNE", 21): 1},
-    "panel_on": {("TUNE", 23): 1},
-    "pg4": {("TUNE", 23): 1, ("TUNE", 24): 4},
-    "pg16": {("TUNE", 23): 1, ("TUNE", 24): 16},
-    "pconv": {("TUNE", 23): 1, ("TUNE", 25): 1},
-    "kb_on": {("TUNE", 26): 1},
+    "skf": {("TUNE", "SPLITK_FUSED"): 1},
+    "wbc16": {("TUNE", "WB_CHUNK"): 16},
+    "wbc64": {("TUNE", "WB_CHUNK"): 64},
+    "cwc16": {("TUNE", "CW_CHUNK"): 16},
+    "cwc64": {("TUNE", "CW_CHUNK"): 64},
+    "c16": {("TUNE", "WB_CHUNK"): 16, ("TUNE", "CW_CHUNK"): 16},
+    "c3_off": {("TUNE", "CONV3X3"): 1},
+    "panel_on": {("TUNE", "PANEL"): 1},
+    "pg4": {("TUNE", "PANEL"): 1, ("TUNE", "PANEL_GROUPS"): 4},
+    "pg16": {("TUNE", "PANEL"): 1, ("TUNE", "PANEL_GROUPS"): 16},
+    "pconv": {("TUNE", "PANEL"): 1, ("TUNE", "PANEL_CONV"): 1},
+    "kb_on": {("TUNE", "ATTN_KEEPPRE"): 1},
     "lnn_off": {("ATTR", "FUSE_LN_NEXT"): False},
     "hd_off": {("ATTR", "HEAD_WGRAD_DEFER"): False},
     "pos_on": {("ATTR", "POS_DEFER"): True},
     "pos_off": {("ATTR", "POS_DEFER"): False},
-    "up2k": {("TUNE", 28): 2048},
-    "up8k": {("TUNE", 28): 8192},
+    "up2k": {("TUNE", "UNPACK_GRID"): 2048},
+    "up8k": {("TUNE", "UNPACK_GRID"): 8192},
     # round 6: round 5's conv weight-gradient unpack (block per 64 chunks) vs the row kernel
-    "unpack_old": {("TUNE", 28): -1},
+    "unpack_old": {("TUNE", "UNPACK_GRID"): -1},
     # round 6: the first blocks' downsample data gradient out of place (+ phase fill)
     "ds_fill": {("RESNET", "DS_DGRAD_INPLACE"): False},
     "lnslab_off": {("ATTR", "LN_BWD_SLABS"): False},
     # grouped projection tiles (RETR_TUNE_GROUP_TILE / _STAGES) re-check
-    "grp_t128": {("TUNE", 0): 128},
-    "grp_t128s1": {("TUNE", 0): 128, ("TUNE", 1): 1},
-    "grp_t128s3": {("TUNE", 0): 128, ("TUNE", 1): 3},
-    "cw_w4": {("TUNE", 29): 1},
-    "cw_w8": {("TUNE", 29): 2},
-    "cw_256": {("TUNE", 29): 3},
+    "grp_t128": {("TUNE", "GROUP_TILE"): 128},
+    "grp_t128s1": {("TUNE", "GROUP_TILE"): 128, ("TUNE", "GROUP_STAGES"): 1},
+    "grp_t128s3": {("TUNE", "GROUP_TILE"): 128, ("TUNE", "GROUP_STAGES"): 3},
+    "cw_w4": {("TUNE", "CW_WAVES"): 1},
+    "cw_w8": {("TUNE", "CW_WAVES"): 2},
+    "cw_256": {("TUNE", "CW_WAVES"): 3},
 }
 
 
@@ -113,12 +113,12 @@ def apply(v):
     ops.LN_BWD_SLABS = True
     resnet.CONV_WGRAD_GROUP = True
     resnet.DS_DGRAD_INPLACE = True
-    load().retr_tune(10, 0)
-    load().retr_tune(12, 0)
-    load().retr_tune(13, 0)
-    load().retr_tune(14, 0)
-    for k in (0, 1, 2, 3, 4, 7, 9, 15, 16, 17, 18, 19, 20, 21, 23, 24, 25, 26, 27, 28, 29, 32, 33):
-        load().retr_tune(k, 0)
+    for name in ("ATTN_SPLIT", "ATTN_FSPLIT", "LIN_SMALL", "SHORTK", "GROUP_TILE",
+                 "GROUP_STAGES", "WGRAD_TILE", "WGRAD_STAGES", "WGRAD_KC", "NT_STORE",
+                 "CONV_WGRAD_TILE", "ADAMW_NT", "WGRAD_B32", "WGRAD_FUSED", "SPLITK_FUSED",
+                 "WB_CHUNK", "CW_CHUNK", "CONV3X3", "PANEL", "PANEL_GROUPS", "PANEL_CONV",
+                 "ATTN_KEEPPRE", "LN_BWD", "UNPACK_GRID", "CW_WAVES", "ROWLN", "LIN_K256"):
+        tune(name, 0)
     ops._SPLITS.clear()                        # split-K counts are cached per shape
     os.environ["RETR_STEM_POOL"] = "1"
     for (table, key), val in VARIANTS[v].items():
@@ -129,7 +129,7 @@ def apply(v):
         elif table == "RESNET":
             setattr(resnet, key, val)
         elif table == "TUNE":
-            load().retr_tune(key, val)
+            tune(key, val)
         else:
             getattr(ops, table)[key] = val
 

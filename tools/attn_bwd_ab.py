@@ -12,7 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from retr_amd import ops  # noqa: E402
-from retr_amd._lib import load  # noqa: E402
+from retr_amd._lib import tuned  # noqa: E402
 from tools.attn_micro import SHAPES, timeit  # noqa: E402
 
 DEV = "cuda"
@@ -36,11 +36,10 @@ def main():
         line = f"{Lq}x{Lk} c{causal}:"
         flop = 10.0 * B * H * Lq * Lk * hd * (0.5 if causal else 1.0)
         for split in (1, 0):
-            load().retr_tune(10, split)
-            t = timeit(lambda: ops.k_attention_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk,
-                                                   hd, kpm, causal, 0.1, 7, dm))
-            line += f"  split{'off' if split == 1 else 'on '} {t:6.1f} us {flop / t / 1e6:6.1f} TF/s"
-        load().retr_tune(10, 0)
+            with tuned(ATTN_SPLIT=split):
+                t = timeit(lambda: ops.k_attention_bwd(q, k, v, o, do, lse, dq, dk, dv, B, H, Lq, Lk,
+                                                       hd, kpm, causal, 0.1, 7, dm))
+                line += f"  split{'off' if split == 1 else 'on '} {t:6.1f} us {flop / t / 1e6:6.1f} TF/s"
         print(line, flush=True)
 
 

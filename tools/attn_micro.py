@@ -13,7 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from retr_amd import ops  # noqa: E402
-from retr_amd._lib import load  # noqa: E402
+from retr_amd._lib import tuned  # noqa: E402
 
 DEV = "cuda"
 SHAPES = [(400, 400, 0), (128, 400, 0), (128, 128, 1)]
@@ -62,10 +62,9 @@ def main():
             fwd, bwd, fl = setup(Lq, Lk, causal)
             out = []
             for sk in (0, 1, 3, 4):
-                load().retr_tune(10, sk)
-                t = timeit(bwd)
-                out.append(f"split{sk}: {t:6.2f} us {2.5 * fl / t / 1e6:5.1f} TF/s")
-            load().retr_tune(10, 0)
+                with tuned(ATTN_SPLIT=sk):
+                    t = timeit(bwd)
+                    out.append(f"split{sk}: {t:6.2f} us {2.5 * fl / t / 1e6:5.1f} TF/s")
             print(f"bwd Lq{Lq:4d} Lk{Lk:4d} causal{causal} | " + " | ".join(out), flush=True)
         return
     if len(sys.argv) > 1 and sys.argv[1] == "fsplit":   # forward key split (RETR_TUNE_ATTN_FSPLIT)
@@ -73,28 +72,26 @@ def main():
             fwd, bwd, fl = setup(Lq, Lk, causal)
             out = []
             for fs in (0, 1, 2, 3, 4):
-                load().retr_tune(12, fs)
-                t = timeit(fwd)
-                out.append(f"fs{fs}: {t:6.2f} us {fl / t / 1e6:5.1f} TF/s")
-            load().retr_tune(12, 0)
+                with tuned(ATTN_FSPLIT=fs):
+                    t = timeit(fwd)
+                    out.append(f"fs{fs}: {t:6.2f} us {fl / t / 1e6:5.1f} TF/s")
             print(f"fwd Lq{Lq:4d} Lk{Lk:4d} causal{causal} | " + " | ".join(out), flush=True)
         return
     if len(sys.argv) > 1:
         which, Lq, Lk, causal, mode = sys.argv[1], *map(int, sys.argv[2:6])
-        load().retr_tune(5, mode)
-        fwd, bwd, fl = setup(Lq, Lk, causal)
-        t = timeit(fwd if which == "fwd" else bwd)
-        print(f"{which} {Lq}x{Lk} c{causal} mode {mode}: {t:.2f} us")
-        return
+        with tuned(ATTN_MODE=mode):
+            fwd, bwd, fl = setup(Lq, Lk, causal)
+            t = timeit(fwd if which == "fwd" else bwd)
+            print(f"{which} {Lq}x{Lk} c{causal} mode {mode}: {t:.2f} us")
+            return
     for Lq, Lk, causal in SHAPES:
         for mode in (1, 2):
-            load().retr_tune(5, mode)
-            fwd, bwd, fl = setup(Lq, Lk, causal)
-            tf, tb = timeit(fwd), timeit(bwd)
-            print(f"Lq{Lq:4d} Lk{Lk:4d} causal{causal} mode{mode}: fwd {tf:7.2f} us "
-                  f"{fl / tf / 1e6:6.1f} TF/s   bwd {tb:7.2f} us {2.5 * fl / tb / 1e6:6.1f} TF/s",
-                  flush=True)
-    load().retr_tune(5, 0)
+            with tuned(ATTN_MODE=mode):
+                fwd, bwd, fl = setup(Lq, Lk, causal)
+                tf, tb = timeit(fwd), timeit(bwd)
+                print(f"Lq{Lq:4d} Lk{Lk:4d} causal{causal} mode{mode}: fwd {tf:7.2f} us "
+                      f"{fl / tf / 1e6:6.1f} TF/s   bwd {tb:7.2f} us {2.5 * fl / tb / 1e6:6.1f} TF/s",
+                      flush=True)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from retr_amd._lib import call, load, ptr, stream  # noqa: E402
+from retr_amd._lib import call, load, ptr, stream, tuned  # noqa: E402
 from tools.conv_micro import timeit  # noqa: E402
 
 SHAPES = [(4096, 4096, 4096), (6400, 256, 2048), (2048, 256, 2048), (6400, 2048, 256),
@@ -38,11 +38,10 @@ def main():
                                      stream()))
             line += f" | retr split{s} {ts:7.1f} us {2 * M * N * K / ts / 1e6:5.0f} TF"
         for v in [int(t) for t in os.environ.get("RETR_VARIANTS", "").split(",") if t]:
-            load().retr_tune(6, v)           # RETR_TUNE_BIG_TILE: launch_big tile override
-            tv = timeit(lambda: call("retr_linear_fwd", 1, ptr(x), K, ptr(w), K, None, ptr(y),
-                                     N, 0, M, N, K, 0, None, 0, 0.0, 0, stream()))
-            load().retr_tune(6, 0)
-            line += f" | t{v} {tv:7.1f} us {2 * M * N * K / tv / 1e6:5.0f} TF"
+            with tuned(BIG_TILE=v):           # RETR_TUNE_BIG_TILE: launch_big tile override
+                tv = timeit(lambda: call("retr_linear_fwd", 1, ptr(x), K, ptr(w), K, None, ptr(y),
+                                         N, 0, M, N, K, 0, None, 0, 0.0, 0, stream()))
+                line += f" | t{v} {tv:7.1f} us {2 * M * N * K / tv / 1e6:5.0f} TF"
         print(line, flush=True)
 
 

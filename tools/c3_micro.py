@@ -13,7 +13,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from retr_amd._lib import call, load, ptr, stream  # noqa: E402
+from retr_amd._lib import call, ptr, stream, tuned  # noqa: E402
 
 DEV = "cuda"
 SHAPES = [(16, 80, 80, 128, 128), (16, 40, 40, 256, 256), (16, 20, 20, 512, 512)]
@@ -44,7 +44,6 @@ def main():
     variants = [int(v) for v in (sys.argv[sys.argv.index("--variants") + 1].split(",")
                                  if "--variants" in sys.argv else "0,1,2,3,4,5,6,7,8".split(","))]
     rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 1
-    lib = load()
     bf = torch.bfloat16
     for nb, H, W, C, Co in SHAPES:
         x = torch.randn(nb, H, W, C, device=DEV).to(bf)
@@ -60,26 +59,23 @@ def main():
             times = {v: [] for v in [-1] + variants}
             for _ in range(rounds):
                 for v in [-1] + variants:
-                    lib.retr_tune(21, 1 if v < 0 else 2)
-                    lib.retr_tune(22, max(v, 0))
-                    if kind == "fwd":
-                        fn = lambda: call("retr_conv2d_fwd", 1, ptr(x), nb, H, W, C, ptr(wf), ptr(b),  # noqa: E731
-                                          None, ptr(y), Co, 3, 3, 1, 1, 1, 1, stream())
-                    else:
-                        fn = lambda: call("retr_conv2d_dgrad", 1, ptr(dy), nb, H, W, C, ptr(wt),  # noqa: E731
-                                          ptr(dx), Co, 3, 3, 1, 1, 1, None, ptr(gate), stream())
-                    try:
-                        times[v].append(timed(fn))
-                    except Exception:   # noqa: BLE001
-                        times[v].append(float("nan"))
+                    with tuned(CONV3X3=1 if v < 0 else 2, C3_TILE=max(v, 0)):
+                        if kind == "fwd":
+                            fn = lambda: call("retr_conv2d_fwd", 1, ptr(x), nb, H, W, C, ptr(wf), ptr(b),  # noqa: E731
+                                              None, ptr(y), Co, 3, 3, 1, 1, 1, 1, stream())
+                        else:
+                            fn = lambda: call("retr_conv2d_dgrad", 1, ptr(dy), nb, H, W, C, ptr(wt),  # noqa: E731
+                                              ptr(dx), Co, 3, 3, 1, 1, 1, None, ptr(gate), stream())
+                        try:
+                            times[v].append(timed(fn))
+                        except Exception:   # noqa: BLE001
+                            times[v].append(float("nan"))
             res = []
             for v, ts in times.items():
                 us = min(ts)
                 med = f"/med {statistics.median(ts):.1f}" if rounds > 1 else ""
                 res.append(f"{'gemm' if v < 0 else 'v%d' % v}={us:.1f}{med}us/{fl / us / 1e6:.0f}TF")
             print(f"{kind:5s} N{nb} {H}x{W} {C}->{Co}: " + "  ".join(res), flush=True)
-    lib.retr_tune(21, 0)
-    lib.retr_tune(22, 0)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@ unfused downsample conv + conv3-with-residual pair, HIP-event timed (tile knob s
 import math
 import torch
 from retr_amd import ops
-from retr_amd._lib import call, ptr, load
+from retr_amd._lib import call, ptr, tuned
 
 DEV, bf = "cuda", torch.bfloat16
 
@@ -51,10 +51,9 @@ def main():
         byts = 2 * M * (C1 + C2 + Co)
         line = f"N{N} {H}x{W} [{C1}|{C2} s{s}]->{Co}: unfused {tu:7.1f} us"
         for knob in (0, 1, 2, 4, 6, 8, 9):
-            load().retr_tune(6, knob)
-            tf = timeit(fused)
-            line += f" | fused t{knob} {tf:6.1f} us {byts / tf / 1e3:5.0f} GB/s"
-        load().retr_tune(6, 0)
+            with tuned(BIG_TILE=knob):
+                tf = timeit(fused)
+                line += f" | fused t{knob} {tf:6.1f} us {byts / tf / 1e3:5.0f} GB/s"
         print(line, flush=True)
 
 

@@ -12,7 +12,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from retr_amd._lib import call, load, ptr, stream  # noqa: E402
+from retr_amd._lib import call, load, ptr, stream, tuned  # noqa: E402
 
 DEV = "cuda"
 BF = 1
@@ -100,14 +100,13 @@ def stem(N=16, H=640):
     for name, fn in cases.items():
         print(f"stem  {name:6s} conversion {timeit(fn):7.1f}us", flush=True)
     for tile in (0, 1, 2, 4, 6):
-        load().retr_tune(6, tile)
-        t7 = timeit(lambda: call("retr_conv2d_fwd", BF, ptr(x8), N, H, H, 8, ptr(w), ptr(b), None,
-                                 ptr(y), 64, 7, 7, 2, 3, 1, 1, stream()))
-        t4 = timeit(lambda: call("retr_conv2d_fwd_out", BF, ptr(xs), N, OH, OH, 16, ptr(w2),
-                                 ptr(b), None, ptr(y), 64, 4, 4, 1, 2, 1, OH, OH, 1, stream()))
-        print(f"stem  t{tile}: 7x7s2 {t7:7.1f}us {fl / t7 / 1e6:4.0f}TF | s2d 4x4 {t4:7.1f}us "
-              f"{fl / t4 / 1e6:4.0f}TF", flush=True)
-    load().retr_tune(6, 0)
+        with tuned(BIG_TILE=tile):
+            t7 = timeit(lambda: call("retr_conv2d_fwd", BF, ptr(x8), N, H, H, 8, ptr(w), ptr(b), None,
+                                     ptr(y), 64, 7, 7, 2, 3, 1, 1, stream()))
+            t4 = timeit(lambda: call("retr_conv2d_fwd_out", BF, ptr(xs), N, OH, OH, 16, ptr(w2),
+                                     ptr(b), None, ptr(y), 64, 4, 4, 1, 2, 1, OH, OH, 1, stream()))
+            print(f"stem  t{tile}: 7x7s2 {t7:7.1f}us {fl / t7 / 1e6:4.0f}TF | s2d 4x4 {t4:7.1f}us "
+                  f"{fl / t4 / 1e6:4.0f}TF", flush=True)
 
 
 def main():
@@ -172,26 +171,20 @@ def main():
             # split-K plan: 0 cost model (default), 1 legacy ceil(512 / tiles), >= 2 forced
             for tile in (2, 1):
                 for plan in (WGRAD_PLANS if only != "wtile" else [0]):
-                    load().retr_tune(8, plan)
-                    load().retr_tune(9, tile)
-                    fn, sp = make_fn()
-                    t = timeit(fn)
-                    out.append(f"{'t64' if tile == 1 else 't128'}/plan{plan}/s{sp}:{t:7.1f}us "
-                               f"{fl / t / 1e6:4.0f}TF")
-            load().retr_tune(8, 0)
-            load().retr_tune(9, 0)
+                    with tuned(CONV_WGRAD_SPLITS=plan, CONV_WGRAD_TILE=tile):
+                        fn, sp = make_fn()
+                        t = timeit(fn)
+                        out.append(f"{'t64' if tile == 1 else 't128'}/plan{plan}/s{sp}:{t:7.1f}us "
+                                   f"{fl / t / 1e6:4.0f}TF")
         for tile, nt in (VARIANTS if kind != "wgrad" else []):
-            load().retr_tune(6, tile)
-            load().retr_tune(7, nt)
-            try:
-                t = timeit(fn)
-            except RuntimeError as e:   # a tile the shape cannot use
-                out.append(f"t{tile}{'nt' if nt else ''}: -- ({str(e)[:30]})")
-                continue
-            out.append(f"t{tile}{'nt' if nt else ''}:{t:7.1f}us {nbytes / t / 1e3:5.0f}GB/s "
-                       f"{fl / t / 1e6:4.0f}TF")
-        load().retr_tune(6, 0)
-        load().retr_tune(7, 0)
+            with tuned(BIG_TILE=tile, NT_STORE=nt):
+                try:
+                    t = timeit(fn)
+                except RuntimeError as e:   # a tile the shape cannot use
+                    out.append(f"t{tile}{'nt' if nt else ''}: -- ({str(e)[:30]})")
+                    continue
+                out.append(f"t{tile}{'nt' if nt else ''}:{t:7.1f}us {nbytes / t / 1e3:5.0f}GB/s "
+                           f"{fl / t / 1e6:4.0f}TF")
         print(f"{kind:5s} N{N} {H}x{W}x{C}->{Co} k{k}s{s} x{extra} | " + " | ".join(out),
               flush=True)
 

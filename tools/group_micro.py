@@ -12,10 +12,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from retr_amd import ops  # noqa: E402
-from retr_amd._lib import load  # noqa: E402
+from retr_amd._lib import tuned  # noqa: E402
 
 DEV = "cuda"
-G_TILE, G_STAGES, W_TILE, W_STAGES, W_KC = range(5)
 
 FWD = {"enc_attn qk|v": [(6400, 512, 256), (6400, 256, 256)],
        "dec_self qk|v": [(2048, 512, 256), (2048, 256, 256)],
@@ -50,10 +49,6 @@ def timeit(fn, n=20):
     return best
 
 
-def tune(knob, v):
-    load().retr_tune(knob, v)
-
-
 def one_wgrad(name, tile, st, kc):
     """A single weight-gradient variant (for rocprofv3 runs: GEMM vs slab-sum split)."""
     bf = torch.bfloat16
@@ -61,11 +56,9 @@ def one_wgrad(name, tile, st, kc):
     items = [(torch.randn(M, N, generator=g).to(DEV).to(bf),
               torch.randn(M, K, generator=g).to(DEV).to(bf), torch.zeros(N, K, device=DEV),
               torch.zeros(N, device=DEV), True) for M, N, K in WGRAD[name]]
-    tune(W_TILE, tile)
-    tune(W_STAGES, st)
-    tune(W_KC, kc)
-    t = timeit(lambda: ops.k_linear_wgrad_group(items))
-    print(f"wgrad {name} {tile} S{st} kc{kc}: {t:.2f} us")
+    with tuned(WGRAD_TILE=tile, WGRAD_STAGES=st, WGRAD_KC=kc):
+        t = timeit(lambda: ops.k_linear_wgrad_group(items))
+        print(f"wgrad {name} {tile} S{st} kc{kc}: {t:.2f} us")
 
 
 def main():
@@ -88,15 +81,12 @@ def main():
         td = timeit(lambda: [ops.k_linear_dgrad(*it) for it in dg])
         print(f"dgrad {name:18s} singles           {td:8.2f} us {flops / td / 1e6:7.1f} TF/s")
         for tile, st in [(64, 2), (64, 4), (128, 1), (128, 2), (128, 3)]:
-            tune(G_TILE, tile)
-            tune(G_STAGES, st)
-            t = timeit(lambda: ops.k_linear_fwd_group(items))
-            td = timeit(lambda: ops.k_linear_dgrad_group(dg))
-            print(f"fwd   {name:18s} group {tile:3d} S{st}      {t:8.2f} us "
-                  f"{flops / t / 1e6:7.1f} TF/s   dgrad {td:8.2f} us {flops / td / 1e6:7.1f} TF/s",
-                  flush=True)
-        tune(G_TILE, 0)
-        tune(G_STAGES, 0)
+            with tuned(GROUP_TILE=tile, GROUP_STAGES=st):
+                t = timeit(lambda: ops.k_linear_fwd_group(items))
+                td = timeit(lambda: ops.k_linear_dgrad_group(dg))
+                print(f"fwd   {name:18s} group {tile:3d} S{st}      {t:8.2f} us "
+                      f"{flops / t / 1e6:7.1f} TF/s   dgrad {td:8.2f} us "
+                      f"{flops / td / 1e6:7.1f} TF/s", flush=True)
     for name, shapes in WGRAD.items():
         items = []
         for M, N, K in shapes:
@@ -107,14 +97,10 @@ def main():
         print(f"wgrad {name:18s} singles           {t:8.2f} us {flops / t / 1e6:7.1f} TF/s")
         for (tile, st), kc in itertools.product([(64, 2), (64, 4), (128, 2), (128, 3)],
                                                 [0, 256, 512, 1024, 2048]):
-            tune(W_TILE, tile)
-            tune(W_STAGES, st)
-            tune(W_KC, kc)
-            t = timeit(lambda: ops.k_linear_wgrad_group(items))
-            print(f"wgrad {name:18s} group {tile:3d} S{st} kc{kc:4d} {t:8.2f} us "
-                  f"{flops / t / 1e6:7.1f} TF/s", flush=True)
-        for k in (W_TILE, W_STAGES, W_KC):
-            tune(k, 0)
+            with tuned(WGRAD_TILE=tile, WGRAD_STAGES=st, WGRAD_KC=kc):
+                t = timeit(lambda: ops.k_linear_wgrad_group(items))
+                print(f"wgrad {name:18s} group {tile:3d} S{st} kc{kc:4d} {t:8.2f} us "
+                      f"{flops / t / 1e6:7.1f} TF/s", flush=True)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from retr_amd._lib import call, load, ptr, stream  # noqa: E402
+from retr_amd._lib import call, ptr, stream, tuned  # noqa: E402
 from tools.conv_micro import timeit  # noqa: E402
 
 
@@ -23,11 +23,10 @@ def main():
         y = torch.empty(M, N, device="cuda")
         out = []
         for tile in tuple(int(t) for t in os.environ.get("HEAD_TILES", "0,1,2,4,6,8,9").split(",")):
-            load().retr_tune(6, tile)
-            t = timeit(lambda: call("retr_linear_fwd", 1, ptr(x), K, ptr(w), K, ptr(b), ptr(y), N,
-                                    1, M, N, K, 0, None, 0, 0.0, 0, stream()))
-            out.append(f"t{tile}: {t:6.1f}us {2 * N * K / t / 1e3:5.0f}GB/s")
-        load().retr_tune(6, 0)
+            with tuned(BIG_TILE=tile):
+                t = timeit(lambda: call("retr_linear_fwd", 1, ptr(x), K, ptr(w), K, ptr(b), ptr(y), N,
+                                        1, M, N, K, 0, None, 0, 0.0, 0, stream()))
+                out.append(f"t{tile}: {t:6.1f}us {2 * N * K / t / 1e3:5.0f}GB/s")
         print(f"M{M} N{N} K{K} | " + " | ".join(out), flush=True)
 
 

@@ -3,7 +3,7 @@ large-GEMM tile knob (RETR_TUNE_BIG_TILE; 0 = built-in rule)."""
 import math
 import torch
 from retr_amd import ops
-from retr_amd._lib import call, ptr, load
+from retr_amd._lib import call, ptr, tuned
 
 DEV, bf = "cuda", torch.bfloat16
 
@@ -38,10 +38,9 @@ def main():
         byts = 2 * N * H * W * (C + Co * (2 if res else 1))
         line = f"N{N} {H}x{W}x{C}->{Co} k{k} res{int(res)}:"
         for knob in (0, 1, 2, 4, 6, 7, 8, 9):
-            load().retr_tune(6, knob)
-            t = timeit(f)
-            line += f" | t{knob} {t:6.1f} us {byts / t / 1e3:5.0f} GB/s"
-        load().retr_tune(6, 0)
+            with tuned(BIG_TILE=knob):
+                t = timeit(f)
+                line += f" | t{knob} {t:6.1f} us {byts / t / 1e3:5.0f} GB/s"
         print(line, flush=True)
 
 

@@ -11,10 +11,9 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from retr_amd._lib import call, load, ptr, stream  # noqa: E402
+from retr_amd._lib import call, ptr, stream, tuned  # noqa: E402
 from tools.conv_micro import timeit  # noqa: E402
 
-KNOB = 33
 SHAPES = [(2048, 256, 256), (6400, 256, 256), (2048, 512, 256), (2048, 64, 256)]
 
 
@@ -44,13 +43,12 @@ def main():
             cols = K if name.startswith("dgrad") else N
             outs, times = [], []
             for v in (1, 2):
-                load().retr_tune(KNOB, v)
-                y = torch.zeros(M, cols, device="cuda", dtype=torch.float32 if f32 else bf)
-                fn(y)
-                torch.cuda.synchronize()
-                outs.append(y.clone())
-                times.append(timeit(lambda: fn(y)))
-            load().retr_tune(KNOB, 0)
+                with tuned(LIN_K256=v):
+                    y = torch.zeros(M, cols, device="cuda", dtype=torch.float32 if f32 else bf)
+                    fn(y)
+                    torch.cuda.synchronize()
+                    outs.append(y.clone())
+                    times.append(timeit(lambda: fn(y)))
             same = "bitwise" if torch.equal(outs[0], outs[1]) else \
                 f"DIFF {(outs[0].float() - outs[1].float()).abs().max().item():.3g}"
             print(f"M{M} N{N} K{K} {name:18s} loop {times[0]:6.2f} us  short {times[1]:6.2f} us  "

@@ -10,7 +10,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from retr_amd._lib import call, load, ptr, stream  # noqa: E402
+from retr_amd._lib import call, load, ptr, stream, tuned  # noqa: E402
 from tools.conv_micro import timeit  # noqa: E402
 
 # (M, N, K, relu, y fp32): FFN expansions (encoder / decoder), the vocabulary head
@@ -38,11 +38,10 @@ def splitk():
                                 0, M, N, K, 0, ptr(res), N, 0.1, 3, ptr(ws), s, stream()))
         out.append(f"split{s}: {t:6.1f}us")
         for tile in (0, 10, 11, 12, 6):
-            load().retr_tune(6, tile)
-            t = timeit(lambda: call("retr_linear_fwd", 1, ptr(x), K, ptr(w), K, ptr(b), ptr(y), N, 0,
-                                    M, N, K, 0, ptr(res), N, 0.1, 3, stream()))
-            out.append(f"t{tile}: {t:6.1f}us")
-        load().retr_tune(6, 0)
+            with tuned(BIG_TILE=tile):
+                t = timeit(lambda: call("retr_linear_fwd", 1, ptr(x), K, ptr(w), K, ptr(b), ptr(y), N, 0,
+                                        M, N, K, 0, ptr(res), N, 0.1, 3, stream()))
+                out.append(f"t{tile}: {t:6.1f}us")
         print(f"fwd   M{M} N{N} K{K} res+drop | " + " | ".join(out), flush=True)
         # data gradient dX[M][N] = dY[M][K] W[K][N] (W row-major [K][N]: w_trans 0), ReLU gate
         dy = torch.randn(M, K, device="cuda").to(bf)
@@ -55,11 +54,10 @@ def splitk():
                                 M, K, N, None, 0, 0, ptr(gate), N, 0, ptr(ws), s, stream()))
         out.append(f"split{s}: {t:6.1f}us")
         for tile in (0, 10, 11, 12, 6):
-            load().retr_tune(6, tile)
-            t = timeit(lambda: call("retr_linear_dgrad", 1, ptr(dy), K, ptr(wk), N, ptr(dx), N, 0,
-                                    M, K, N, None, 0, 0, ptr(gate), N, 0, stream()))
-            out.append(f"t{tile}: {t:6.1f}us")
-        load().retr_tune(6, 0)
+            with tuned(BIG_TILE=tile):
+                t = timeit(lambda: call("retr_linear_dgrad", 1, ptr(dy), K, ptr(wk), N, ptr(dx), N, 0,
+                                        M, K, N, None, 0, 0, ptr(gate), N, 0, stream()))
+                out.append(f"t{tile}: {t:6.1f}us")
         print(f"dgrad M{M} N{N} K{K} gate     | " + " | ".join(out), flush=True)
 
 
@@ -79,11 +77,10 @@ def main():
         y = torch.empty(M, N, device="cuda", dtype=torch.float32 if f32 else bf)
         out = []
         for tile in tiles:
-            load().retr_tune(6, tile)
-            t = timeit(lambda: call("retr_linear_fwd", 1, ptr(x), K, ptr(w), K, ptr(b), ptr(y), N,
-                                    f32, M, N, K, relu, None, 0, 0.0, 0, stream()))
-            out.append(f"t{tile}: {t:6.1f}us {2 * M * N * K / t / 1e6:4.0f}TF")
-        load().retr_tune(6, 0)
+            with tuned(BIG_TILE=tile):
+                t = timeit(lambda: call("retr_linear_fwd", 1, ptr(x), K, ptr(w), K, ptr(b), ptr(y), N,
+                                        f32, M, N, K, relu, None, 0, 0.0, 0, stream()))
+                out.append(f"t{tile}: {t:6.1f}us {2 * M * N * K / t / 1e6:4.0f}TF")
         print(f"fwd M{M} N{N} K{K} | " + " | ".join(out), flush=True)
 
 

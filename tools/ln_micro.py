@@ -11,7 +11,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from retr_amd._lib import call, load, ptr, stream  # noqa: E402
+from retr_amd._lib import call, load, ptr, stream, tuned  # noqa: E402
 from tools.conv_micro import timeit  # noqa: E402
 
 
@@ -32,13 +32,12 @@ def main():
         npar = ctypes.c_int(0)
         out = []
         for cfg in (0, 1, 2, 3, 4, 5, 6):
-            load().retr_tune(27, cfg)
-            t = timeit(lambda: call("retr_layernorm_bwd2", 1, ptr(dy), ptr(dy2), C, ptr(x), C,
-                                    ptr(g), ptr(mean), ptr(rstd), M, C, ptr(dx), C, ptr(add),
-                                    None, None, ptr(ws), ptr(dxd), C, 0.1, 7,
-                                    ctypes.addressof(npar), stream()))
-            out.append(f"c{cfg}: {t:6.2f}us")
-        load().retr_tune(27, 0)
+            with tuned(LN_BWD=cfg):
+                t = timeit(lambda: call("retr_layernorm_bwd2", 1, ptr(dy), ptr(dy2), C, ptr(x), C,
+                                        ptr(g), ptr(mean), ptr(rstd), M, C, ptr(dx), C, ptr(add),
+                                        None, None, ptr(ws), ptr(dxd), C, 0.1, 7,
+                                        ctypes.addressof(npar), stream()))
+                out.append(f"c{cfg}: {t:6.2f}us")
         print(f"ln_bwd2 M{M} C{C} | " + " | ".join(out), flush=True)
 
 

@@ -15,7 +15,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from retr_amd import _lib  # noqa: E402
-from retr_amd._lib import ptr  # noqa: E402
+from retr_amd._lib import ptr, tuned  # noqa: E402
 
 DEV = "cuda"
 
@@ -72,16 +72,14 @@ def main():
         for name, knob, splits in (("slab2", 1, 2), ("slab4", 1, 4), ("rowln", 2, 1)):
             d = _lib.LnOut(ptr(gamma), ptr(beta), 1e-5, 1, ptr(ly), ptr(ly2), N, ptr(pos), period,
                            ptr(mean), ptr(rstd))
-            lib.retr_tune(32, knob)
-
-            def fused(st, d=d, splits=splits):
-                rc = lib.retr_linear_fwd_splitk_ln(1, ptr(x), K, ptr(w), K, ptr(bias), ptr(y), N,
-                                                   M, N, K, 0, ptr(res), N, 0.1, 1234,
-                                                   ptr(ws) if splits > 1 else None, splits,
-                                                   ctypes.byref(d), st)
-                assert rc == 0, lib.retr_last_error()
-            res_t[name] = timed(fused)
-            lib.retr_tune(32, 0)
+            with tuned(ROWLN=knob):
+                def fused(st, d=d, splits=splits):
+                    rc = lib.retr_linear_fwd_splitk_ln(1, ptr(x), K, ptr(w), K, ptr(bias), ptr(y), N,
+                                                       M, N, K, 0, ptr(res), N, 0.1, 1234,
+                                                       ptr(ws) if splits > 1 else None, splits,
+                                                       ctypes.byref(d), st)
+                    assert rc == 0, lib.retr_last_error()
+                res_t[name] = timed(fused)
         print(f"M{M} N256 K256 +LN: " + "  ".join(f"{k} {v:6.2f} us" for k, v in res_t.items()),
               flush=True)
 

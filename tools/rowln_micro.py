@@ -16,10 +16,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from retr_amd import _lib  # noqa: E402
-from retr_amd._lib import ptr  # noqa: E402
+from retr_amd._lib import ptr, tuned  # noqa: E402
 
 DEV = "cuda"
-KNOB = 32                      # RETR_TUNE_ROWLN
 
 
 def main():
@@ -45,47 +44,45 @@ def main():
             rstd = torch.empty(M, device=DEV)
             d = _lib.LnOut(ptr(gamma), ptr(beta), 1e-5, 1, ptr(ly), ptr(ly2), N, ptr(pos), period,
                            ptr(mean), ptr(rstd))
-            lib.retr_tune(KNOB, v)
+            with tuned(ROWLN=v):
+                def call():
+                    rc = lib.retr_linear_fwd_splitk_ln(1, ptr(x), K, ptr(w), K, ptr(bias), ptr(y), N,
+                                                       M, N, K, 0, ptr(res), N, 0.1, 1234, ptr(ws),
+                                                       splits, ctypes.byref(d), st)
+                    assert rc == 0, lib.retr_last_error()
 
-            def call():
-                rc = lib.retr_linear_fwd_splitk_ln(1, ptr(x), K, ptr(w), K, ptr(bias), ptr(y), N,
-                                                   M, N, K, 0, ptr(res), N, 0.1, 1234, ptr(ws),
-                                                   splits, ctypes.byref(d), st)
-                assert rc == 0, lib.retr_last_error()
-
-            call()
-            torch.cuda.synchronize()
-            gr = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                st_s = s.cuda_stream
-
-                def call_s():
-                    rc = lib.retr_linear_fwd_splitk_ln(1, ptr(x), K, ptr(w), K, ptr(bias), ptr(y),
-                                                       N, M, N, K, 0, ptr(res), N, 0.1, 1234,
-                                                       ptr(ws), splits, ctypes.byref(d), st_s)
-                    assert rc == 0
-                with torch.cuda.graph(gr, stream=s):
-                    for _ in range(20):
-                        call_s()
-            torch.cuda.current_stream().wait_stream(s)
-            best = 1e9
-            for _ in range(5):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                gr.replay()
-                e1.record()
+                call()
                 torch.cuda.synchronize()
-                best = min(best, e0.elapsed_time(e1) * 1e3 / 20)
-            outs[v] = (y.clone(), ly.float().clone(), ly2.float().clone(), mean.clone(),
-                       rstd.clone())
-            err = max(((a - b).abs().max() / b.abs().max()).item()
-                      for a, b in zip(outs[v], outs[1]))
-            flops = 2.0 * M * N * K
-            print(f"M{M} N{N} K{K} +LN  variant {v}: {best:7.2f} us  {flops / best / 1e6:7.1f} TF/s"
-                  f"  max rel diff vs 1: {err:.2e}", flush=True)
-        lib.retr_tune(KNOB, 0)
+                gr = torch.cuda.CUDAGraph()
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    st_s = s.cuda_stream
+
+                    def call_s():
+                        rc = lib.retr_linear_fwd_splitk_ln(1, ptr(x), K, ptr(w), K, ptr(bias), ptr(y),
+                                                           N, M, N, K, 0, ptr(res), N, 0.1, 1234,
+                                                           ptr(ws), splits, ctypes.byref(d), st_s)
+                        assert rc == 0
+                    with torch.cuda.graph(gr, stream=s):
+                        for _ in range(20):
+                            call_s()
+                torch.cuda.current_stream().wait_stream(s)
+                best = 1e9
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    gr.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    best = min(best, e0.elapsed_time(e1) * 1e3 / 20)
+                outs[v] = (y.clone(), ly.float().clone(), ly2.float().clone(), mean.clone(),
+                           rstd.clone())
+                err = max(((a - b).abs().max() / b.abs().max()).item()
+                          for a, b in zip(outs[v], outs[1]))
+                flops = 2.0 * M * N * K
+                print(f"M{M} N{N} K{K} +LN  variant {v}: {best:7.2f} us  {flops / best / 1e6:7.1f} TF/s"
+                      f"  max rel diff vs 1: {err:.2e}", flush=True)
 
 
 if __name__ == "__main__":

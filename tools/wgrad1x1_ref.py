@@ -10,7 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from retr_amd import ops  # noqa: E402
-from retr_amd._lib import call, load, ptr  # noqa: E402
+from retr_amd._lib import call, load, ptr, tuned  # noqa: E402
 
 SHAPES = [  # (N, H, Ci, Co)
     (16, 40, 256, 1024), (16, 80, 128, 512), (16, 40, 1024, 256), (16, 80, 512, 128),
@@ -42,15 +42,14 @@ def main():
         fl = 2.0 * P * Ci * Co
         line = f"P{P} Co{Co} Ci{Ci}:"
         for t in tiles:
-            lib.retr_tune(9, t)
-            s = lib.retr_conv2d_wgrad_splits(1, N, H, H, Ci, Co, 1, 1, 1, 0, 1)
-            ws = torch.empty(s, Co, Ci, device="cuda")
-            f = lambda: call("retr_conv2d_wgrad", 1, ptr(dy), ptr(x), N, H, H, Ci, ptr(ws), Co,  # noqa: E731
-                             1, 1, 1, 0, 1, ops._st())
-            f()
-            us = timeit(f)
-            line += f" retr[t{t} s{s}] {us:6.1f} us {fl / us / 1e6:4.0f} TF |"
-        lib.retr_tune(9, 0)
+            with tuned(CONV_WGRAD_TILE=t):
+                s = lib.retr_conv2d_wgrad_splits(1, N, H, H, Ci, Co, 1, 1, 1, 0, 1)
+                ws = torch.empty(s, Co, Ci, device="cuda")
+                f = lambda: call("retr_conv2d_wgrad", 1, ptr(dy), ptr(x), N, H, H, Ci, ptr(ws), Co,  # noqa: E731
+                                 1, 1, 1, 0, 1, ops._st())
+                f()
+                us = timeit(f)
+                line += f" retr[t{t} s{s}] {us:6.1f} us {fl / us / 1e6:4.0f} TF |"
         dyt = dy.t()
         us = timeit(lambda: torch.mm(dyt, x))
         line += f" hipBLASLt {us:6.1f} us {fl / us / 1e6:4.0f} TF"

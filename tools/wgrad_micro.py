@@ -11,7 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from retr_amd import ops  # noqa: E402
-from retr_amd._lib import load  # noqa: E402
+from retr_amd._lib import tuned  # noqa: E402
 from tools.conv_micro import timeit  # noqa: E402
 
 
@@ -25,16 +25,15 @@ def main():
         ref = None
         line = f"wgrad M{M} N{N} K{K}:"
         for v in (1, 0, 2, 4):
-            load().retr_tune(11, v)
-            dw.zero_()
-            db.zero_()
-            ops.k_linear_wgrad(dy, x, dw, db)
-            torch.cuda.synchronize()
-            err = 0.0 if ref is None else ((dw - ref).norm() / ref.norm()).item()
-            ref = dw.clone() if ref is None else ref
-            t = timeit(lambda: ops.k_linear_wgrad(dy, x, dw, db))
-            line += f"  v{v} {t:6.1f} us {2 * M * N * K / t / 1e6:5.0f} TF err {err:.1e}"
-        load().retr_tune(11, 0)
+            with tuned(LIN_WGRAD=v):
+                dw.zero_()
+                db.zero_()
+                ops.k_linear_wgrad(dy, x, dw, db)
+                torch.cuda.synchronize()
+                err = 0.0 if ref is None else ((dw - ref).norm() / ref.norm()).item()
+                ref = dw.clone() if ref is None else ref
+                t = timeit(lambda: ops.k_linear_wgrad(dy, x, dw, db))
+                line += f"  v{v} {t:6.1f} us {2 * M * N * K / t / 1e6:5.0f} TF err {err:.1e}"
         print(line, flush=True)
 
 
