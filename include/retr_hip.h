@@ -619,6 +619,34 @@ int retr_greedy_select2(int dtype, const void* logits, long ld, int B, int V, vo
                         unsigned char* finished, int* done, long long* tok, int write_all,
                         void* stream);
 
+/* ---- sampling decode (new capability): temperature, top-k, nucleus; one draw per row --------
+ * logits [M][ld] (dtype), the first V columns of a row valid (ld >= V, ld % 8 == 0, 16-byte
+ * aligned base).  The sampling parameters are read from DEVICE memory by the kernel, so one
+ * captured graph serves every setting: fparams = float[2] {inv_temperature, top_p},
+ * iparams = long long[2] {top_k, seed}.  `step` is the decode step (a host scalar, like the
+ * greedy bookkeeping's i).  finished [M], logprob [M] and n_kept [M] may be NULL.
+ * Per row r, in fp32, x_j the logit as fp32:
+ *   1. z_j = x_j * inv_temperature (one multiply).
+ *   2. The words are ranked by z descending, then index ascending (first-index tie rule).
+ *   3. top-k: the first min(top_k, V) of that order are kept; top_k <= 0 or >= V keeps all.
+ *   4. top-p: with the probabilities renormalised over the top-k set, the shortest prefix of
+ *      the order whose mass is >= top_p is kept, at least one word; top_p >= 1 keeps all.
+ *      n_kept[r] = the length of the final prefix.
+ *   5. Gumbel-max draw: s = seed ^ (draw * 0x9E3779B97F4A7C15) (64-bit, wrapping),
+ *      draw = step * M + r; per kept word j: h = the library's 64 -> 32-bit counter hash of
+ *      (s, j), u = ((h >> 9) + 0.5) * 2^-23, g = -log(-log(u)); pred[r] = the kept word with the
+ *      largest z_j + g_j, the lower index on ties.
+ *   6. logprob[r] = log-softmax of the RAW logits (temperature 1, all V words) at pred[r]: the
+ *      model's own log-likelihood of the drawn word; 0 where finished[r] != 0 on entry.
+ *   7. top_k == 1 gives the first-index argmax of the logits, whatever the other parameters.
+ *   8. A -inf logit has probability 0 and is never drawn while the row has a finite one.
+ * Two launches on the same inputs give the same bits (fixed-order reductions, no atomics).
+ * Rows of up to 32768 words are held in registers; longer rows are re-read per pass. */
+int retr_sample_rows(int dtype, const void* logits, long ld, int M, int V,
+                     const float* fparams, const long long* iparams, int step,
+                     const unsigned char* finished, long long* pred, float* logprob,
+                     int* n_kept, void* stream);
+
 /* ---- elementwise helpers --------------------------------------------------------------- */
 /* Encoder output without a final LayerNorm (pre_norm=False; models/ConcatTransformer.py:24,
  * 105-106): y = cast(x), y2 = cast(x + pos[row % period]) (either output may be NULL) */

@@ -18,6 +18,10 @@ replayed, so a step costs its kernels' device time, not ~100 host launches.  The
 attention (retr_attention_decode) reduces keys in a different order than the tiled training
 kernel, so logits agree with the full recompute to rounding, and the token ids agree with the
 reference algorithm run by the CPU oracle (tests/test_gpu_model.py).
+
+Two decoders beyond the reference run on the same steps with another selection kernel:
+``beam_search`` (IncrementalBeam) and ``sample`` (IncrementalSampler: temperature, top-k and
+nucleus sampling, several samples per image, per-token log-probabilities).
 """
 import torch
 
@@ -599,6 +603,11 @@ class IncrementalGreedy:
         if T != qpos_w.shape[0]:
             raise RuntimeError(f"The size of tensor a ({T}) must match the size of tensor b "
                                f"({qpos_w.shape[0]}) at non-singleton dimension 0")
+        return self._run(mem, mem_pos, kpm, B, S, T, bos_token, eos_token, poll)
+
+    def _run(self, mem, mem_pos, kpm, B, S, T, bos_token, eos_token, poll):
+        """Decode B memories (mem / mem_pos [B*S, C], kpm [B, S]) into captions."""
+        model, cd = self.model, self.cdtype
         C = mem.shape[1]
         n = self._split(B)
         if n > 1:
@@ -771,6 +780,121 @@ class IncrementalBeam(IncrementalGreedy):
             cap[:, done + 1:] = 0
         self.last_scores = scores.gather(1, best[:, None])[:, 0]
         return cap
+
+
+def _check_sampling_args(temperature, top_k, top_p, num_samples):
+    """ValueError for sampling arguments outside their domain (host only: before any GPU work)."""
+    import math
+    if not math.isfinite(temperature) or temperature < 0:
+        raise ValueError(f"temperature must be finite and >= 0, got {temperature}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0 (0: no top-k), got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    if int(num_samples) != num_samples or num_samples < 1:
+        raise ValueError(f"num_samples must be an integer >= 1, got {num_samples}")
+
+
+class IncrementalSampler(IncrementalGreedy):
+    """KV-cache sampling decoder (new capability: the reference decodes greedily only):
+    temperature, top-k and nucleus filtering and one Gumbel-max draw per row and step
+    (``retr_sample_rows``, csrc/sample.hip; contract in include/retr_hip.h), then greedy's
+    finished / early-exit / column bookkeeping unchanged (``retr_greedy_update``).  A row keeps
+    drawing after its EOS until every row is finished, as greedy keeps writing its argmax;
+    ``prune_cap_ids`` cuts there.
+
+    ``num_samples = n`` decodes n independent rows per image: the encoder runs once on the B
+    images, their memories are repeated, and the result is [B*n, T], image-major.
+
+    The sampling parameters live in device buffers that the kernel reads (``samp_f`` =
+    {1 / temperature, top_p}, ``samp_i`` = {top_k, seed}), filled before every replay and never
+    captured: the graphs bake in only the step index and the shapes, so one capture serves
+    every setting, and ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` may be reassigned
+    between calls.  ``temperature == 0`` and ``top_k == 1`` are greedy, token for token.  The
+    draw of step i, row r is number i * R + r of the seed's stream (R = the call's rows), so a
+    batch is never split into row groups.
+
+    After a call ``last_token_logprobs`` [R, T-1] holds, per written column up to and
+    including a row's first EOS, log p(token) under the model -- the log-softmax of the raw
+    logits (temperature 1, whole vocabulary) -- and 0 elsewhere: ``score_expressions``'
+    convention."""
+
+    def __init__(self, model, temperature=1.0, top_k=0, top_p=1.0, num_samples=1, seed=None,
+                 use_graphs=True, fused=True):
+        _check_sampling_args(temperature, top_k, top_p, num_samples)
+        super().__init__(model, use_graphs, fused)
+        self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
+        self.num_samples = int(num_samples)
+        self.seed = seed
+        self.last_seed = None
+        self.last_token_logprobs = None
+        self.last_done = -1
+
+    def _new_state(self, B, S, T, C, F, L, V, cd, dev):
+        st = _DecodeState(B, S, T, C, F, L, V, cd, dev)
+        st.samp_f = torch.zeros(2, dtype=torch.float32, device=dev)
+        st.samp_i = torch.zeros(2, dtype=torch.int64, device=dev)
+        # tok_lp [R, T] (column i+1: the token written by step i), stored step-major so that a
+        # step's R values are the contiguous vector the kernel writes
+        st.tok_lp = torch.zeros(T, st.R, dtype=torch.float32, device=dev).t()
+        st.n_kept = torch.zeros(st.R, dtype=torch.int32, device=dev)
+        return st
+
+    def _params(self):
+        """(samp_f, samp_i) host values of this call."""
+        _check_sampling_args(self.temperature, self.top_k, self.top_p, self.num_samples)
+        t, k = float(self.temperature), int(self.top_k)
+        if t == 0.0:
+            t, k = 1.0, 1                    # greedy: the first-index argmax of the raw logits
+        one = torch.ones((), dtype=torch.float32)
+        inv_t = float(one / torch.tensor(t, dtype=torch.float32))    # a float32 value
+        seed = self.seed
+        if seed is None:      # torch's default CPU generator: torch.manual_seed repeats a run
+            seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64))
+        seed = (int(seed) + 2 ** 63) % 2 ** 64 - 2 ** 63             # as an int64
+        self.last_seed = seed
+        return (torch.tensor([inv_t, float(self.top_p)], dtype=torch.float32),
+                torch.tensor([k, seed], dtype=torch.int64))
+
+    def _reset(self, st, bos_token):
+        """Greedy's reset, zeroed log-probabilities, and the call's parameters into the device
+        buffers (stream work before the replay; _reset never runs inside a capture)."""
+        super()._reset(st, bos_token)
+        st.tok_lp.zero_()
+        st.samp_f.copy_(self._call_params[0])
+        st.samp_i.copy_(self._call_params[1])
+
+    def _split(self, B):
+        return 1        # the draw counter is defined on the whole batch
+
+    def _run(self, mem, mem_pos, kpm, B, S, T, bos_token, eos_token, poll):
+        self._call_params = self._params()
+        n = self.num_samples
+        if n > 1:       # rows b*n .. b*n+n-1 decode image b: its memory, n times
+            C = mem.shape[1]
+            mem = mem.view(B, S, C).repeat_interleave(n, 0).view(B * n * S, C)
+            mem_pos = mem_pos.view(B, S, C).repeat_interleave(n, 0).view(B * n * S, C)
+            kpm = kpm.repeat_interleave(n, 0)
+        return super()._run(mem, mem_pos, kpm, B * n, S, T, bos_token, eos_token, poll)
+
+    def _select(self, st, i, V, eos_token, s):
+        """One draw per row, then greedy's bookkeeping on the drawn tokens."""
+        call("retr_sample_rows", dcode(self.cdtype), ptr(st.logits), st.Vp, st.R, V,
+             ptr(st.samp_f), ptr(st.samp_i), i, ptr(st.finished), ptr(st.pred),
+             ptr(st.tok_lp[:, i + 1]), ptr(st.n_kept), s)
+        call("retr_greedy_update", ptr(st.pred), st.R, st.T, i, int(eos_token), ptr(st.caption),
+             ptr(st.finished), ptr(st.done), ptr(st.tok), s)
+
+    def _result(self, st):
+        done = int(st.done.item())
+        lp = st.tok_lp[:, 1:].clone()
+        if done >= 0:
+            lp[:, done:] = 0          # step `done` ended the decode: it wrote no column
+        self.last_token_logprobs = lp.contiguous()
+        self.last_done = done         # the step that ended the decode early, or -1
+        return st.caption.clone()
+
+
 def _full_forward_greedy(samples, model, max_len, bos_token, eos_token, device):
     """The reference algorithm (decode.py:59-81) on the MI355X kernels: one full model forward
     per step.  Used when the model is in training mode (dropout active) and for parity tests."""
@@ -819,6 +943,43 @@ def beam_decoding(samples, model, tokenizer, max_len=20, beam_size=5, clean=True
     caption_idx = beam_search(samples, model, max_len=max_len, beam_size=beam_size,
                               device=device, bos_token=bos_token, eos_token=eos_token,
                               length_penalty=length_penalty)
+    caption_idx = caption_idx.cpu().detach().numpy().tolist()
+    pruned = prune_cap_ids(caption_idx, clean=clean, pad_token=pad_token, bos_token=bos_token,
+                           eos_token=eos_token)
+    return idx2sents(pruned, tokenizer)
+
+
+def sample(samples, model, max_len=20, temperature=1.0, top_k=0, top_p=1.0, num_samples=1,
+           seed=None, device="auto", bos_token=1, eos_token=2, return_logprobs=False):
+    """Sampling decode for a batch of samples (new; the reference has greedy only): per step
+    the logits are divided by ``temperature``, cut to the ``top_k`` best words (0: all) and to
+    the smallest set holding ``top_p`` of the remaining mass (1: all), and one word is drawn.
+    Same inputs and caption format as ``greedy``, [B * num_samples, max_len] image-major;
+    ``temperature=0`` or ``top_k=1`` returns exactly greedy's ids.  ``seed=None`` takes a seed
+    from torch's default CPU generator.  With ``return_logprobs`` also (token_logprob
+    [R, max_len-1], seq_logprob [R]): the model's own log-probability (temperature 1, no
+    filter) of every written token up to a row's first EOS, in ``score_expressions``'
+    convention."""
+    _check_sampling_args(temperature, top_k, top_p, num_samples)
+    if model.training:
+        raise RuntimeError("sample runs in eval mode (model.eval())")
+    if device == "auto":
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    samples = [s.to(device) for s in samples]
+    dec = IncrementalSampler(model, temperature, top_k, top_p, num_samples, seed)
+    ids = dec(samples, max_len, bos_token, eos_token)
+    if return_logprobs:
+        return ids, dec.last_token_logprobs, dec.last_token_logprobs.sum(1)
+    return ids
+
+
+def sample_decoding(samples, model, tokenizer, max_len=20, temperature=1.0, top_k=0, top_p=1.0,
+                    num_samples=1, seed=None, clean=True, pad_token=0, bos_token=1, eos_token=2,
+                    device="auto"):
+    """greedy_decoding's wrapper (decode.py:112-128) around ``sample``."""
+    caption_idx = sample(samples, model, max_len=max_len, temperature=temperature, top_k=top_k,
+                         top_p=top_p, num_samples=num_samples, seed=seed, device=device,
+                         bos_token=bos_token, eos_token=eos_token)
     caption_idx = caption_idx.cpu().detach().numpy().tolist()
     pruned = prune_cap_ids(caption_idx, clean=clean, pad_token=pad_token, bos_token=bos_token,
                            eos_token=eos_token)
