@@ -594,11 +594,15 @@ int retr_argmax_rows_ws(int dtype, const void* x, long ld, int M, int V, long lo
 
 /* greedy bookkeeping for step i (eval_utils/decode.py:72-79) on device */
 /* ---- beam search (new capability; reference decode.py has greedy only) -------------------
- * per row of x [M][ld]: the K best (index, log-softmax value), first index on ties (K <= 8) */
+ * per row of x [M][ld]: the K best (index, log-softmax value), first index on ties (K <= 8).
+ * Only the first V columns of a row are read.  As for retr_sample_rows (point 8 below), a -inf
+ * logit has probability 0: it ranks after every finite word, in index order, with log-softmax
+ * -inf, and the values of the finite words stay finite (a row needs one finite word). */
 int retr_topk_rows(int dtype, const void* x, long ld, int M, int V, int K, int* idx,
                    float* logprob, void* stream);
 /* one beam step for B images x K beams: select survivors from the retr_topk_rows candidates,
- * reorder hist [B*K][T] / anc [B*K][T], append step i's token, done = i once all finished */
+ * reorder hist [B*K][T] / anc [B*K][T], append step i's token, done = i once all finished;
+ * nothing is written once done >= 0.  1 <= K <= 8, i + 1 < T, K * T * 12 <= 65536 (LDS). */
 int retr_beam_select(const int* cand_tok, const float* cand_lp, int B, int K, int i, int T,
                      long long eos, float* scores, unsigned char* finished, long long* hist,
                      int* anc, long long* tok, unsigned char* item_done, int* done,

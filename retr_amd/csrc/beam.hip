@@ -6,6 +6,10 @@
 // all candidates (ties: lower parent beam, then better-ranked token) survive.  With K = 1 the
 // chosen token is exactly the first-index argmax of the logits, so beam=1 == greedy.
 //
+// -inf logits (retr_topk_rows adopts point 8 of the retr_sample_rows contract, retr_hip.h): a
+// -inf word has probability 0, ranks after every finite word in index order with log-softmax
+// -inf, and the finite words' values stay finite; a row keeps at least one finite word.
+//
 // KV caches are never copied when beams are reordered: anc[r][t] names the cache row that holds
 // position t of beam row r (the row whose beam computed it at step t), and the decode attention
 // kernel reads keys / values through it (retr_attention_decode's `anc`).
@@ -68,7 +72,9 @@ topk_kernel(const T* x, long ld, int V, int* idx_out, float* lp_out) {
   };
   auto offer = [&](float v, int i) {
     if (v > mx) {
-      sum = sum * __expf(mx - v) + 1.f;
+      // first finite word: whatever the -inf words before it left in sum (exp(-inf - -inf) is
+      // NaN) is dropped, as offer8 does
+      sum = mx == -INFINITY ? 1.f : sum * __expf(mx - v) + 1.f;
       mx = v;
     } else {
       sum += __expf(v - mx);
@@ -449,8 +455,21 @@ int retr_beam_select(const int* cand_tok, const float* cand_lp, int B, int K, in
                      int* anc, long long* tok, unsigned char* item_done, int* done,
                      void* stream) {
   RETR_REQUIRE(K >= 1 && K <= kMaxK && i >= 0 && i + 1 < T, "beam_select: bad K/i/T");
-  size_t lds = 128 + (size_t)K * T * (sizeof(long long) + sizeof(int));
-  RETR_REQUIRE(lds <= 65536, "beam_select: K*T too large");
+  // the staged hist + anc rows (12 bytes per position) may fill 64 KiB; with the 128-byte
+  // selection header and the kernel's static arrays the largest blocks pass the 64 KiB a kernel
+  // gets by default, which gfx950 (160 KiB per CU) grants on request
+  constexpr size_t kRowBytes = 65536;
+  const size_t rows = (size_t)K * T * (sizeof(long long) + sizeof(int));
+  RETR_REQUIRE(rows <= kRowBytes, "beam_select: K*T too large");
+  const size_t lds = 128 + rows;
+  if (lds > 65536 - 1024) {
+    static bool attr_set = false;   // host attribute, once (capture-safe)
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)beam_select_kernel,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(128 + kRowBytes));
+      attr_set = true;
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(256), lds, st, cand_tok, cand_lp, B, K, i,
                      T, eos, scores, finished, hist, anc, tok, item_done, done);
